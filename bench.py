@@ -18,6 +18,11 @@ torch.distributed traffic is the barriers and the gather of the ranks' elapsed t
 --genome humanlike swaps the i.i.d. reference for one with human-like repeat content; --image /
 BWAHIP_REF_IMG uses an existing index image (reads sampled from its packed reference);
 LIBBWA_PATH / BWA_ORACLE_SRC make a stock libbwa the CPU baseline and parity checker.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  Everything else it can measure or
+check (host_to_host, the roofline pass, the CPU baseline and parity samples, `secondary.humanlike`, the in-process
+multi-device handle) runs only with --full.  --dump-outputs DIR writes what the last timed step computed (a fixed,
+seeded sample of the response records, plus a CRC per block of reads over the whole response) as .npy files.
 """
 import argparse
 import ctypes
@@ -82,7 +87,7 @@ def synth_genome(torch, dev, total_bp, n_contigs, seed):
     while done < n_rep and total_bp > 20000:
         l = int(torch.randint(300, 6000, (1,), generator=hg))
         src = int(torch.randint(0, total_bp - l, (1,), generator=hg)); dst = int(torch.randint(0, total_bp - l, (1,), generator=hg))
-        seg = codes[src:src + l].clone()
+        seg = codes[src:src + l]                                  # (a view: torch.where below makes the copy before codes changes)
         mut = torch.rand(l, generator=g, device=dev) < 0.03
         seg = torch.where(mut, (seg + torch.randint(1, 4, (l,), dtype=torch.uint8, generator=g, device=dev)) % 4, seg)
         if int(torch.randint(0, 2, (1,), generator=hg)):
@@ -297,6 +302,45 @@ def synth_long_reads(torch, dev, codes, contigs, n, length, seed):
     return payload
 
 
+DUMP_SAMPLE = 1 << 17          # reads whose records --dump-outputs writes in full
+DUMP_BLOCK = 1 << 16           # reads per CRC-32 block over the whole response
+
+
+def dump_outputs(lib, batch, n_reads, out_dir):
+    """--dump-outputs: the response of the last timed step (what jnibwa_createAlignments would hand its caller: one int32 stream
+    of per-read records, jnibwa.c:99-124) as float64 .npy files, every value exact:
+      read_index      the sampled reads (fixed seed, sorted), DUMP_SAMPLE of them at most
+      record_offsets  offsets of their records in record_words (one more than reads)
+      record_words    their records' int32 words, concatenated
+      block_crc32     CRC-32 of the records of every DUMP_BLOCK consecutive reads, over the whole response
+      response_info   [reads, response bytes]"""
+    import numpy as np
+    import zlib
+    import bwalib as B
+    if not os.path.exists(B.ORACLE_LIB):
+        B.build_oracle()
+    total = lib.bwamem_hip_batch_result_bytes(batch)
+    buf = np.empty(max(total, 4), dtype=np.uint8)
+    if lib.bwamem_hip_batch_download(batch, buf.ctypes.data) != 0:
+        raise SystemExit("download of the timed batch's response failed")
+    offs = np.empty(n_reads + 1, dtype=np.int64)
+    ro = ctypes.CDLL(B.ORACLE_LIB).oracle_response_offsets           # the record walk, in C
+    ro.restype = ctypes.c_int
+    ro.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p]
+    if ro(buf.ctypes.data, total, n_reads, offs.ctypes.data) != 0 or offs[n_reads] != total or (offs % 4).any():
+        raise SystemExit("response of the timed batch does not parse")
+    words = buf[:total].view(np.int32)
+    pick = np.sort(np.random.default_rng(0x5EED).choice(n_reads, size=min(n_reads, DUMP_SAMPLE), replace=False))
+    lo, hi = offs[pick] // 4, offs[pick + 1] // 4
+    rec_off = np.concatenate([[0], np.cumsum(hi - lo)])
+    sel = np.repeat(lo - rec_off[:-1], hi - lo) + np.arange(rec_off[-1])
+    crc = [zlib.crc32(memoryview(buf[offs[b]:offs[min(b + DUMP_BLOCK, n_reads)]])) for b in range(0, n_reads, DUMP_BLOCK)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("read_index", pick), ("record_offsets", rec_off), ("record_words", words[sel]), ("block_crc32", crc),
+                    ("response_info", [n_reads, total])):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1, help="ranks = GPUs of this node; > 1 without a launcher: this process starts them itself")
@@ -326,6 +370,10 @@ def parse_args():
     ap.add_argument("--dump-only", action="store_true", help="with --keep-image / --dump-request: stop once the files are written (profiling helper for the torch-free driver)")
     ap.add_argument("--image", default=os.environ.get("BWAHIP_REF_IMG"), help="use an existing .img (e.g. GATK's Homo_sapiens_assembly38.fasta.img) instead of "
                     "the synthetic genome; reads are sampled from its packed reference (default: $BWAHIP_REF_IMG)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: host_to_host calls, the roofline pass, the CPU "
+                    "baseline and parity samples, the in-process multi-device handle and (default single-GPU command) `secondary.humanlike`")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float64): the response records of a fixed, seeded sample of reads and a CRC-32 per block of reads over the whole response")
     args = ap.parse_args()
     if args.cpu_sample is None:
         args.cpu_sample = 5_000 if args.ont else 400_000
@@ -396,7 +444,7 @@ def run_with_secondary(args):
         raise SystemExit(rc or 1)
     t0 = time.time()
     try:
-        rc2, sec = child(["--genome", "humanlike", "--steps", "3", "--warmup", "2", "--h2h-calls", "2", "--cpu-sample", "100000", "--cpu-reps", "1",
+        rc2, sec = child(["--full", "--genome", "humanlike", "--steps", "3", "--warmup", "2", "--h2h-calls", "2", "--cpu-sample", "100000", "--cpu-reps", "1",
                           "--no-secondary", "--in-process-devices", "none", "--reads", str(args.reads), "--read-len", str(args.read_len)], 1500)
         if rc2 == 0 and sec is not None:
             out["secondary"] = {"humanlike": {
@@ -418,7 +466,7 @@ def main():
     args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ:
         launch_ranks(args.gpus)
-    if (not args.no_secondary and "RANK" not in os.environ and args.gpus <= 1 and not (args.paired or args.ont or args.image or args.dump_only or args.pestat)
+    if (args.full and not args.no_secondary and "RANK" not in os.environ and args.gpus <= 1 and not (args.paired or args.ont or args.image or args.dump_only or args.pestat)
             and args.genome == "iid" and args.genome_bp >= 1_000_000_000):
         run_with_secondary(args)
 
@@ -578,17 +626,20 @@ def main():
     lib.bwamem_hip_stats_enable(0)
     result_bytes = lib.bwamem_hip_batch_result_bytes(batch)
     note("%d timed steps done (%.1f ms per step)" % (args.steps, elapsed / args.steps * 1e3))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(lib, batch, R, args.dump_outputs)
+        note("outputs of the last timed step written to %s" % args.dump_outputs)
 
     # ---- the same batch through the drop-in entry point itself: jnibwa_createAlignments, host request in, malloc'ed host
     # response out (jnibwa.c:197-235) -- every rank at once, so that at N > 1 the ranks share the host's memory and PCIe
     # like N GATK executors would.  Reported next to `value`, never as `value` (which is quoted with the request resident).
     h2h = None
     inproc_spec = args.in_process_devices
-    if inproc_spec == "auto":
+    if inproc_spec == "auto" and args.full:
         inproc_spec = "all" if lib.bwamem_hip_device_count() > 1 else "none"
-    want_inproc = rank == 0 and world == 1 and inproc_spec != "none" and args.h2h_calls > 0
+    want_inproc = args.full and rank == 0 and world == 1 and inproc_spec != "none" and args.h2h_calls > 0
     keep_full = keep_resident = None
-    if args.h2h_calls > 0:
+    if args.full and args.h2h_calls > 0:
         full = np.empty(4 + R * (L + 1), dtype=np.uint8)
         full[:4] = np.frombuffer(struct.pack("<i", R), dtype=np.uint8)
         full[4:] = payload.reshape(-1).cpu().numpy()
@@ -624,7 +675,7 @@ def main():
 
     # keep the records of the LAST reads of the timed batch (four tiles and a seeding chunk in flight) for the parity check below
     tail_bytes, S2 = None, 0
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and (not args.paired or pes is not None):   # (paired with inferred statistics: the batch-wide ones differ from a slice's)
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and (not args.paired or pes is not None):   # (paired with inferred statistics: the batch-wide ones differ from a slice's)
         import bwalib as B
         if not os.path.exists(B.ORACLE_LIB):
             B.build_oracle()
@@ -641,28 +692,40 @@ def main():
                 raise SystemExit("response of the timed batch does not parse")
             tail_bytes = bytes(memoryview(buf)[offs[R - S2]:offs[R]])
         del buf
-    # Roofline pass (untimed): during the timed steps several tiles are in flight on separate streams, so the
-    # HIP-event interval of one launch also contains other tiles' kernels.  One extra step with a single tile in
-    # flight gives per-launch durations that mean what rocprofv3 --kernel-trace reports for the same kernel.
-    streams_env = os.environ.get("BWAMEM_HIP_STREAMS")
-    os.environ["BWAMEM_HIP_STREAMS"] = "1"
-    os.environ["BWAMEM_HIP_SEED_AHEAD"] = "0"            # seeding chunks strictly between the tiles, nothing else on the GPU
-    lib.bwamem_hip_stats_enable(1)
-    lib.bwamem_hip_stats_reset()
-    step()
-    torch.cuda.synchronize()
-    st = Stats(); lib.bwamem_hip_stats_get(ctypes.byref(st))
-    note("roofline pass (one tile in flight) done")
-    del os.environ["BWAMEM_HIP_SEED_AHEAD"]
-    if streams_env is None:
-        del os.environ["BWAMEM_HIP_STREAMS"]
-    else:
-        os.environ["BWAMEM_HIP_STREAMS"] = streams_env
-    lib.bwamem_hip_stats_enable(0)
+    if args.full:
+        # Roofline pass (untimed): during the timed steps several tiles are in flight on separate streams, so the
+        # HIP-event interval of one launch also contains other tiles' kernels.  One extra step with a single tile in
+        # flight gives per-launch durations that mean what rocprofv3 --kernel-trace reports for the same kernel.
+        streams_env = os.environ.get("BWAMEM_HIP_STREAMS")
+        os.environ["BWAMEM_HIP_STREAMS"] = "1"
+        os.environ["BWAMEM_HIP_SEED_AHEAD"] = "0"            # seeding chunks strictly between the tiles, nothing else on the GPU
+        lib.bwamem_hip_stats_enable(1)
+        lib.bwamem_hip_stats_reset()
+        step()
+        torch.cuda.synchronize()
+        st = Stats(); lib.bwamem_hip_stats_get(ctypes.byref(st))
+        note("roofline pass (one tile in flight) done")
+        del os.environ["BWAMEM_HIP_SEED_AHEAD"]
+        if streams_env is None:
+            del os.environ["BWAMEM_HIP_STREAMS"]
+        else:
+            os.environ["BWAMEM_HIP_STREAMS"] = streams_env
+        lib.bwamem_hip_stats_enable(0)
 
     out = None
     if rank == 0:
         value = world * R * args.steps / elapsed
+        out = {
+            "metric": "150bp reads aligned/sec vs GRCh38-scale reference (1/2/4/8 MI355X)", "value": value, "unit": "reads/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32/int64", "data": "synthetic",
+            "config": {"workload": "%d x %dbp %s synthetic reads per GPU vs %s, full index in HBM" % (R, L, "paired-end (2 x %d pairs)" % (R // 2) if args.paired else "single-end ONT-style (8 %% sub, 3 %% ins, 3 %% del)" if args.ont else "single-end", genome_desc),
+                       "reads_per_gpu": R, "read_len": L, "genome_bp": args.genome_bp, "genome": "image" if args.image else args.genome, "index_build_s": round(t_index, 1), "index_builder_s": round(t_index_build, 1) if t_index_build is not None else None, "response_bytes": result_bytes,
+                       "parallelism": "read-sharded x%d, no collectives" % world, "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "paired_end": bool(args.paired), "insert_size_statistics": ("supplied " + args.pestat) if (args.paired and args.pestat) else ("inferred per call" if args.paired else None),
+                       "value_is": "device-resident rate: request already in HBM when the timed region starts, response left in HBM (the bench contract); the rate through jnibwa_createAlignments itself is `host_to_host`"},
+            "per_rank": {"reads_per_s": [R * args.steps / x for x in per_rank], "ms_per_step_min": min(per_rank) / args.steps * 1e3, "ms_per_step_max": max(per_rank) / args.steps * 1e3},
+        }
+    if rank == 0 and args.full:
         kern = dict(encode=st.ms_encode, seed=st.ms_seed, sa=st.ms_sa, chain=st.ms_chain, extend=st.ms_extend, post=st.ms_post, final=st.ms_final, pack=st.ms_pack, other=st.ms_other)
         # roofline of the occurrence-table gather kernel (k_seed): 2 x 32-byte occ blocks (device layout) per interval extension
         n_launch = max(1, st.n_launch_seed)
@@ -683,15 +746,7 @@ def main():
             except (OSError, KeyError, ValueError):
                 pass
         nr = max(1, st.n_reads)
-        out = {
-            "metric": "150bp reads aligned/sec vs GRCh38-scale reference (1/2/4/8 MI355X)", "value": value, "unit": "reads/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32/int64", "data": "synthetic",
-            "config": {"workload": "%d x %dbp %s synthetic reads per GPU vs %s, full index in HBM" % (R, L, "paired-end (2 x %d pairs)" % (R // 2) if args.paired else "single-end ONT-style (8 %% sub, 3 %% ins, 3 %% del)" if args.ont else "single-end", genome_desc),
-                       "reads_per_gpu": R, "read_len": L, "genome_bp": args.genome_bp, "genome": "image" if args.image else args.genome, "index_build_s": round(t_index, 1), "index_builder_s": round(t_index_build, 1) if t_index_build is not None else None, "response_bytes": result_bytes,
-                       "parallelism": "read-sharded x%d, no collectives" % world, "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "paired_end": bool(args.paired), "insert_size_statistics": ("supplied " + args.pestat) if (args.paired and args.pestat) else ("inferred per call" if args.paired else None),
-                       "value_is": "device-resident rate: request already in HBM when the timed region starts, response left in HBM (the bench contract); the rate through jnibwa_createAlignments itself is `host_to_host`"},
-            "per_rank": {"reads_per_s": [R * args.steps / x for x in per_rank], "ms_per_step_min": min(per_rank) / args.steps * 1e3, "ms_per_step_max": max(per_rank) / args.steps * 1e3},
+        out.update({
             "value_at_boundary": h2h["reads_per_s"] if h2h else None,
             "value_at_boundary_is": "reads/s through jnibwa_createAlignments itself (SURVEY.md 8(d): wall inside the call, H2D and D2H included): what a GATK caller gets; details in `host_to_host`",
             "host_to_host": h2h,
@@ -702,10 +757,10 @@ def main():
             "tiles_in_flight_timed": int(os.environ.get("BWAMEM_HIP_STREAMS", "4")),
             "counters": {"n_ext": int(st.n_ext), "n_lf": int(st.n_lf), "n_sa": int(st.n_sa), "n_dp_cells": int(st.n_dp_cells), "tiles": int(st.n_tiles), "retries": int(st.n_retries)},
             "per_read": {"ext": st.n_ext / nr, "sa_lookups": st.n_sa / nr, "dp_cells": st.n_dp_cells / nr, "response_bytes": result_bytes / max(1, R)},
-        }
+        })
 
     # ---- CPU baseline + parity sample (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         import bwalib as B
         if not os.path.exists(B.ORACLE_LIB):
             B.build_oracle()
@@ -807,6 +862,7 @@ def main():
             pass
     if dist is not None:
         dist.destroy_process_group()
+    note("done")
 
 
 if __name__ == "__main__":

@@ -210,7 +210,7 @@ bool build_index_files(const std::string& fasta, const std::string& prefix, std:
     const bool force_host = eb && !strcmp(eb, "host"), force_dev = eb && !strcmp(eb, "device");
     if (!force_host && device_index_available()) {
         std::string derr;
-        if (device_index_pieces(fp.fwd, fp.p, &derr)) return write_index_files(fp.p, prefix, err);
+        if (device_index_pieces(fp.fwd.data(), (uint64_t)fp.fwd.size(), fp.p, &derr)) return write_index_files(fp.p, prefix, err);
         if (force_dev) { if (err) *err = "device index builder: " + derr; return false; }
         fprintf(stderr, "[bwamem_hip] device index builder failed (%s): building on the host\n", derr.c_str());
     } else if (force_dev) { if (err) *err = "BWAMEM_HIP_INDEX_BUILDER=device but no HIP device is visible"; return false; }

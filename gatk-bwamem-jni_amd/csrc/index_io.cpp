@@ -10,6 +10,8 @@
 #include <stdlib.h>
 #include <fstream>
 #include <sstream>
+#include <algorithm>
+#include <thread>
 
 namespace {
 
@@ -93,13 +95,13 @@ bool parse_index_image(const uint8_t* mem, size_t l_mem, HostIndex& ix)
     return k == l_mem;                       // upstream asserts exactly this
 }
 
-std::vector<uint8_t> image_from_pieces(const IndexPieces& p)
+namespace {
+
+// the image around its three large arrays: the bwt header (before the bwt words and SA samples) and the bns section (between
+// them and the pac)
+std::vector<uint8_t> image_head(const IndexPieces& p)
 {
-    size_t strbytes = 0;
-    for (const ContigInfo& c : p.contigs) strbytes += c.name.size() + c.anno.size() + 2;
-    size_t total = BWT_HDR + p.bwt.size() * 4 + p.sa.size() * 8 + BNS_HDR + p.holes.size() * AMB_REC
-                 + p.contigs.size() * ANN_REC + strbytes + (size_t)(p.l_pac / 4 + 1);
-    std::vector<uint8_t> img(total, 0);
+    std::vector<uint8_t> img(BWT_HDR, 0);
     uint8_t* m = img.data();
     wr<uint64_t>(m + BWT_PRIMARY, p.primary);
     for (int i = 0; i < 5; ++i) wr<uint64_t>(m + BWT_L2 + 8 * i, p.L2[i]);
@@ -113,9 +115,16 @@ std::vector<uint8_t> image_from_pieces(const IndexPieces& p)
     }
     wr<int32_t>(m + BWT_SAINTV, p.sa_intv);
     wr<uint64_t>(m + BWT_NSA, (uint64_t)p.sa.size());
-    size_t k = BWT_HDR;
-    memcpy(m + k, p.bwt.data(), p.bwt.size() * 4); k += p.bwt.size() * 4;
-    memcpy(m + k, p.sa.data(), p.sa.size() * 8); k += p.sa.size() * 8;
+    return img;
+}
+
+std::vector<uint8_t> image_bns(const IndexPieces& p)
+{
+    size_t strbytes = 0;
+    for (const ContigInfo& c : p.contigs) strbytes += c.name.size() + c.anno.size() + 2;
+    std::vector<uint8_t> img(BNS_HDR + p.holes.size() * AMB_REC + p.contigs.size() * ANN_REC + strbytes, 0);
+    uint8_t* m = img.data();
+    size_t k = 0;
     wr<int64_t>(m + k + BNS_LPAC, p.l_pac);
     wr<int32_t>(m + k + BNS_NSEQS, (int32_t)p.contigs.size());
     wr<uint32_t>(m + k + BNS_SEED, p.seed);
@@ -134,8 +143,49 @@ std::vector<uint8_t> image_from_pieces(const IndexPieces& p)
         memcpy(m + k, c.name.c_str(), c.name.size() + 1); k += c.name.size() + 1;
         memcpy(m + k, c.anno.c_str(), c.anno.size() + 1); k += c.anno.size() + 1;
     }
-    memcpy(m + k, p.pac.data(), (size_t)(p.l_pac / 4 + 1));
     return img;
+}
+
+} // namespace
+
+std::vector<uint8_t> image_from_pieces(const IndexPieces& p)
+{
+    const std::vector<uint8_t> head = image_head(p), bns = image_bns(p);
+    const size_t n_pac = (size_t)(p.l_pac / 4 + 1);
+    std::vector<uint8_t> img(head.size() + p.bwt.size() * 4 + p.sa.size() * 8 + bns.size() + n_pac);
+    uint8_t* m = img.data();
+    memcpy(m, head.data(), head.size()); m += head.size();
+    memcpy(m, p.bwt.data(), p.bwt.size() * 4); m += p.bwt.size() * 4;
+    memcpy(m, p.sa.data(), p.sa.size() * 8); m += p.sa.size() * 8;
+    memcpy(m, bns.data(), bns.size()); m += bns.size();
+    memcpy(m, p.pac.data(), n_pac);
+    return img;
+}
+
+bool write_image_file(const IndexPieces& p, const char* path)
+{
+    FILE* fp = fopen(path, "wb");
+    if (!fp) return false;
+    const std::vector<uint8_t> head = image_head(p), bns = image_bns(p);
+    const size_t n_pac = (size_t)(p.l_pac / 4 + 1);
+    bool ok = fwrite(head.data(), 1, head.size(), fp) == head.size()
+           && fwrite(p.bwt.data(), 4, p.bwt.size(), fp) == p.bwt.size()
+           && fwrite(p.sa.data(), 8, p.sa.size(), fp) == p.sa.size()
+           && fwrite(bns.data(), 1, bns.size(), fp) == bns.size()
+           && fwrite(p.pac.data(), 1, n_pac, fp) == n_pac;
+    return fclose(fp) == 0 && ok;
+}
+
+void host_parallel_for(int64_t n, int64_t align, const std::function<void(int64_t, int64_t)>& f)
+{
+    const unsigned hw = std::thread::hardware_concurrency();
+    const int64_t nt = n < (1 << 24) ? 1 : std::max<int64_t>(1, std::min<int64_t>(16, hw ? hw : 1));
+    int64_t step = (n + nt - 1) / nt;
+    step = (step + align - 1) / align * align;
+    std::vector<std::thread> th;
+    for (int64_t lo = step; lo < n; lo += step) th.emplace_back(f, lo, std::min(n, lo + step));
+    f(0, std::min(n, step));
+    for (std::thread& t : th) t.join();
 }
 
 std::vector<uint8_t> image_from_index_files(const std::string& prefix, std::string* err)

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <string>
 #include <vector>
+#include <functional>
 
 struct ContigInfo {
     int64_t offset; int32_t len, n_ambs; uint32_t gi; int32_t is_alt;
@@ -43,11 +44,15 @@ struct IndexPieces {
     std::vector<uint8_t> pac;          // l_pac/4+1 bytes
 };
 std::vector<uint8_t> image_from_pieces(const IndexPieces& p);
+// the same bytes streamed to a file, without the image ever existing in memory as a whole; false on I/O error
+bool write_image_file(const IndexPieces& p, const char* path);
+// f(lo, hi) over [0, n) in chunks whose bounds are multiples of align, on up to 16 host threads (one below 16 M elements)
+void host_parallel_for(int64_t n, int64_t align, const std::function<void(int64_t, int64_t)>& f);
 
 // fasta -> <prefix>.{pac,ann,amb,bwt,sa}; replaces upstream bwa_idx_build (bwtindex.c).  The suffix array, BWT, occ checkpoints
 // and SA samples are computed on the device when one is visible (k_index.hip), on the host otherwise or when
 // BWAMEM_HIP_INDEX_BUILDER=host; the files are byte-identical either way.
 bool build_index_files(const std::string& fasta, const std::string& prefix, std::string* err);
-// k_index.hip: is there a device to build on / the device half of the builder (fwd: one code 0..3 per forward-strand base)
+// k_index.hip: is there a device to build on / the device half of the builder (fwd: l codes 0..3, one per forward-strand base)
 bool device_index_available();
-bool device_index_pieces(const std::vector<uint8_t>& fwd, IndexPieces& out, std::string* err);
+bool device_index_pieces(const uint8_t* fwd, uint64_t l, IndexPieces& out, std::string* err);

@@ -21,6 +21,7 @@
 #include <string.h>
 #include <string>
 #include <vector>
+#include <mutex>
 #include "index_io.h"
 
 #define IDX_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (err) *err = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } } while (0)
@@ -58,26 +59,41 @@ __device__ inline uint64_t key32(const uint64_t* W, uint64_t p)
 }
 
 // positions whose first two bases are bucket b (any order: the refinement below leaves no ties, so the suffix array does not
-// depend on it): one atomic per wavefront
-__global__ void k_bucket_collect(const uint64_t* W, uint64_t n, int b, uint64_t* pos, unsigned long long* count)
+// depend on it).  A workgroup of COLLECT_BLOCK threads takes COLLECT_PER_THREAD x COLLECT_BLOCK positions at a time and reserves
+// their stretch of pos with ONE atomic: a bucket holds a sixteenth of the text, so an atomic per wavefront would put ~10^8
+// atomics a launch on the one counter, and they serialise there
+constexpr int COLLECT_BLOCK = 256, COLLECT_PER_THREAD = 16;
+__global__ void __launch_bounds__(COLLECT_BLOCK) k_bucket_collect(const uint64_t* W, uint64_t n, int b, uint64_t* pos, unsigned long long* count)
 {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x; i0 < n; i0 += stride) {       // (a grid of n threads would exceed the 2^32 work-items of a launch)
-        const uint64_t i = i0 + threadIdx.x;
-        bool hit = false;
-        if (i < n) {
-            const uint64_t w = W[i >> 5]; const int s = (int)(i & 31) << 1;
-            const uint32_t c0 = (uint32_t)(w >> (62 - s)) & 3u;
-            const uint32_t c1 = i + 1 < n ? (uint32_t)(key32(W, i + 1) >> 62) : 0u;     // (beyond the end counts as 'A', as in the keys)
-            hit = (int)(c0 * 4 + c1) == b;
+    __shared__ uint32_t scan[COLLECT_BLOCK];
+    __shared__ unsigned long long base;
+    const uint64_t tile = (uint64_t)COLLECT_BLOCK * COLLECT_PER_THREAD;
+    for (uint64_t t0 = (uint64_t)blockIdx.x * tile; t0 < n; t0 += (uint64_t)gridDim.x * tile) {     // (uniform across the workgroup)
+        uint32_t hits = 0;                    // bit j: position t0 + j * COLLECT_BLOCK + threadIdx.x is in the bucket
+        for (int j = 0; j < COLLECT_PER_THREAD; ++j) {
+            const uint64_t i = t0 + (uint64_t)j * COLLECT_BLOCK + threadIdx.x;
+            if (i < n) {
+                const uint64_t w = W[i >> 5]; const int s = (int)(i & 31) << 1;
+                const uint32_t c0 = (uint32_t)(w >> (62 - s)) & 3u;
+                const uint32_t c1 = i + 1 < n ? (uint32_t)(key32(W, i + 1) >> 62) : 0u;     // (beyond the end counts as 'A', as in the keys)
+                if ((int)(c0 * 4 + c1) == b) hits |= 1u << j;
+            }
         }
-        const unsigned long long m = __ballot(hit);
-        if (!m) continue;
-        const int lane = threadIdx.x & 63;
-        unsigned long long base = 0;
-        if (lane == __ffsll((long long)m) - 1) base = atomicAdd(count, (unsigned long long)__popcll(m));
-        base = __shfl(base, __ffsll((long long)m) - 1);
-        if (hit) pos[base + __popcll(m & ((1ull << lane) - 1))] = i;
+        const uint32_t c = (uint32_t)__popc(hits);
+        scan[threadIdx.x] = c;
+        __syncthreads();
+        for (int d = 1; d < COLLECT_BLOCK; d <<= 1) {          // inclusive scan of the threads' hit counts
+            const uint32_t v = (int)threadIdx.x >= d ? scan[threadIdx.x - d] : 0u;
+            __syncthreads();
+            scan[threadIdx.x] += v;
+            __syncthreads();
+        }
+        if (threadIdx.x == COLLECT_BLOCK - 1) base = scan[threadIdx.x] ? atomicAdd(count, (unsigned long long)scan[threadIdx.x]) : 0ull;
+        __syncthreads();
+        unsigned long long o = base + scan[threadIdx.x] - c;
+        for (int j = 0; j < COLLECT_PER_THREAD; ++j)
+            if (hits >> j & 1u) pos[o++] = t0 + (uint64_t)j * COLLECT_BLOCK + threadIdx.x;
+        __syncthreads();                                        // (scan and base are reused by the next tile)
     }
 }
 
@@ -202,13 +218,13 @@ bool device_index_available()
 }
 
 // fwd: the forward strand, one code 0..3 per base (ambiguous bases already replaced).  Fills primary, L2, seq_len, bwt, sa, sa_intv.
-bool device_index_pieces(const std::vector<uint8_t>& fwd_h, IndexPieces& out, std::string* err)
+bool device_index_pieces(const uint8_t* fwd_h, uint64_t l, IndexPieces& out, std::string* err)
 {
-    const uint64_t l = fwd_h.size(), n = 2 * l;
+    const uint64_t n = 2 * l;
     if (l == 0) { if (err) *err = "empty reference"; return false; }
     Buf fwd, Wb, sa;
     if (!fwd.ensure(l + 64) || !Wb.ensure(((n + 31) / 32 + 4) * 8) || !sa.ensure(n * 8 + 64)) { if (err) *err = "out of device memory"; return false; }
-    IDX_OK(hipMemcpy(fwd.p, fwd_h.data(), l, hipMemcpyHostToDevice));
+    IDX_OK(hipMemcpy(fwd.p, fwd_h, l, hipMemcpyHostToDevice));
     const uint64_t n_words = (n + 31) / 32 + 4;
     hipLaunchKernelGGL(k_pack_words, grid_for(n_words, 256), dim3(256), 0, 0, fwd.as<uint8_t>(), l, n_words, Wb.as<uint64_t>());
     const uint64_t* W = Wb.as<uint64_t>();
@@ -227,7 +243,7 @@ bool device_index_pieces(const std::vector<uint8_t>& fwd_h, IndexPieces& out, st
         {
             // counting pass: same kernel with a null destination would need a branch; use a small trick -- collect into SA + at
             // directly (the stretch [at, at + m) belongs to this bucket, and nothing beyond `at` has been written yet)
-            hipLaunchKernelGGL(k_bucket_collect, grid_for(n, 256), dim3(256), 0, 0, W, n, b, SA + at, cnt.as<unsigned long long>());
+            hipLaunchKernelGGL(k_bucket_collect, grid_for((n + COLLECT_PER_THREAD - 1) / COLLECT_PER_THREAD, COLLECT_BLOCK), dim3(COLLECT_BLOCK), 0, 0, W, n, b, SA + at, cnt.as<unsigned long long>());
             IDX_OK(hipGetLastError());
             IDX_OK(hipMemcpy(&m64, cnt.p, 8, hipMemcpyDeviceToHost));
         }
@@ -323,7 +339,13 @@ bool device_index_pieces(const std::vector<uint8_t>& fwd_h, IndexPieces& out, st
     out.seq_len = n;
     {   // L2 from the forward strand's base counts (the reverse complement mirrors them)
         uint64_t c[4] = {0, 0, 0, 0};
-        for (uint8_t x : fwd_h) ++c[x];
+        std::mutex mu;
+        host_parallel_for((int64_t)l, 1, [&](int64_t lo, int64_t hi) {
+            uint64_t t[4] = {0, 0, 0, 0};
+            for (int64_t i = lo; i < hi; ++i) ++t[fwd_h[i]];
+            std::lock_guard<std::mutex> lk(mu);
+            for (int s = 0; s < 4; ++s) c[s] += t[s];
+        });
         const uint64_t t4[4] = { c[0] + c[3], c[1] + c[2], c[2] + c[1], c[3] + c[0] };
         out.L2[0] = 0;
         for (int s = 0; s < 4; ++s) out.L2[s + 1] = out.L2[s] + t4[s];

@@ -1600,17 +1600,13 @@ int bwamem_hip_build_image(const uint8_t* codes, int64_t l_pac, int32_t n_contig
         }
         if (off != l_pac) return -1;
         p.l_pac = l_pac; p.seed = 11;
-        std::vector<uint8_t> fwd(codes, codes + l_pac);
         p.pac.assign((size_t)(l_pac / 4 + 1), 0);
-        for (int64_t i = 0; i < l_pac; ++i) p.pac[i >> 2] |= (uint8_t)((fwd[i] & 3) << ((~i & 3) << 1));
+        host_parallel_for(l_pac, 4, [&](int64_t lo, int64_t hi) {           // (chunks of whole pac bytes)
+            for (int64_t i = lo; i < hi; ++i) p.pac[i >> 2] |= (uint8_t)((codes[i] & 3) << ((~i & 3) << 1));
+        });
         std::string err;
-        if (!device_index_pieces(fwd, p, &err)) { fprintf(stderr, "[bwamem_hip] device index builder: %s\n", err.c_str()); return -1; }
-        std::vector<uint8_t>().swap(fwd);
-        const std::vector<uint8_t> img = image_from_pieces(p);
-        FILE* fp = fopen(img_path, "wb");
-        if (!fp) return -1;
-        const bool ok = fwrite(img.data(), 1, img.size(), fp) == img.size();
-        return fclose(fp) == 0 && ok ? 0 : -1;
+        if (!device_index_pieces(codes, (uint64_t)l_pac, p, &err)) { fprintf(stderr, "[bwamem_hip] device index builder: %s\n", err.c_str()); return -1; }
+        return write_image_file(p, img_path) ? 0 : -1;
     });
 }
 

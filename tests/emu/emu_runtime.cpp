@@ -135,4 +135,4 @@ void launch(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& bo
 #include <vector>
 #include "index_io.h"
 bool device_index_available() { return false; }
-bool device_index_pieces(const std::vector<uint8_t>&, IndexPieces&, std::string* err) { if (err) *err = "no device in the emulation build"; return false; }
+bool device_index_pieces(const uint8_t*, uint64_t, IndexPieces&, std::string* err) { if (err) *err = "no device in the emulation build"; return false; }

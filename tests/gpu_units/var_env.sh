@@ -2,8 +2,9 @@
 set -e
 R=$GRAFT_REPO_ROOT
 name=$1; shift
-mkdir -p $R/gpurun_out/var
+OUT=${BENCH_VAR_OUT:-$R/bench_var}
+mkdir -p $OUT
 for v in "$@"; do
-  env $name=$v python3 $R/bench.py --gpus 1 --steps 6 --warmup 3 --no-secondary --cpu-sample 20000 --cpu-reps 1 --h2h-calls 1 > $R/gpurun_out/var/env_$v.json 2> $R/gpurun_out/var/env_$v.err
+  env $name=$v python3 $R/bench.py --full --gpus 1 --steps 6 --warmup 3 --no-secondary --cpu-sample 20000 --cpu-reps 1 --h2h-calls 1 > $OUT/env_$v.json 2> $OUT/env_$v.err
   echo done $v
 done

@@ -442,7 +442,7 @@ def test_bench_launcher_starts_its_own_ranks(tmp_path):
     env = dict(os.environ, BENCH_REHEARSAL="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(B.ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--reads", "100000",
+    r = subprocess.run([sys.executable, os.path.join(B.ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1", "--warmup", "1", "--reads", "100000",
                         "--genome-bp", "8000000", "--contigs", "4", "--cpu-sample", "0", "--h2h-calls", "2"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -451,6 +451,34 @@ def test_bench_launcher_starts_its_own_ranks(tmp_path):
     out = json.loads(line[0])
     assert out["n_gpus"] == 2 and len(out["per_rank"]["reads_per_s"]) == 2
     assert out["value"] > 0 and out["host_to_host"]["reads_per_s"] > 0 and out["host_to_host"]["identical_to_resident_response"] is True
+
+
+def test_bench_plain_run_dumps_identical_outputs(tmp_path):
+    """A plain bench run (no --full) prints the headline line without the --full measurements, times exactly --steps steps,
+    and --dump-outputs writes the last timed step's records; two runs with the same arguments dump identical arrays."""
+    import subprocess
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_REHEARSAL"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        r = subprocess.run([sys.executable, os.path.join(B.ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "100000",
+                            "--genome-bp", "8000000", "--contigs", "4", "--dump-outputs", d], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(line) == 1, r.stdout
+        out = json.loads(line[0])
+        assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "reads/s" and out["higher_is_better"] is True
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 100000) < 1
+        assert not {"host_to_host", "roofline", "cpu_baseline", "parity_sample", "secondary", "in_process_multi_device"} & set(out)
+        dumps.append({f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["block_crc32.npy", "read_index.npy", "record_offsets.npy", "record_words.npy", "response_info.npy"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert list(a["response_info.npy"]) == [100000, out["config"]["response_bytes"]] and len(a["read_index.npy"]) == 100000
+    assert all(np.array_equal(a[f], b[f]) for f in a)
 
 
 def test_parity_long_reads_with_long_deletions(hip_lib, oracle, medium_genome, monkeypatch):
@@ -510,7 +538,7 @@ def test_bench_on_an_existing_image_with_a_stock_library_hook(small_genome, tmp_
     env = dict(os.environ, LIBBWA_PATH=B.HIP_LIB)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BENCH_REHEARSAL"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(B.ROOT, "bench.py"), "--image", img, "--reads", "20000", "--steps", "1", "--warmup", "0",
+    r = subprocess.run([sys.executable, os.path.join(B.ROOT, "bench.py"), "--full", "--image", img, "--reads", "20000", "--steps", "1", "--warmup", "0",
                         "--cpu-sample", "3000", "--cpu-reps", "1", "--h2h-calls", "1"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -528,7 +556,7 @@ def test_paired_end_on_repeat_rich_genome(tmp_path):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(B.ROOT, "bench.py"), "--paired", "--genome", "humanlike", "--genome-bp", "16000000", "--contigs", "3",
+    r = subprocess.run([sys.executable, os.path.join(B.ROOT, "bench.py"), "--full", "--paired", "--genome", "humanlike", "--genome-bp", "16000000", "--contigs", "3",
                         "--reads", "60000", "--steps", "1", "--warmup", "1", "--cpu-sample", "60000", "--cpu-reps", "1", "--h2h-calls", "2"],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -55,3 +55,38 @@ def test_torch_builder_on_the_gpu_matches_host_builder(hip_lib, workdir, monkeyp
     pieces = G.build_pieces(fwd)
     G.write_image(fa + ".torch.img", pieces, [(n, len(s)) for n, s in seqs])
     assert open(fa + ".torch.img", "rb").read() == open(fa + ".img", "rb").read()
+
+
+BUILD_IMAGE_CODE = r"""
+import ctypes, os, sys
+import torch                                     # (first: the process then has one HIP runtime, torch's, as in bench.py)
+sys.path[:0] = [%(tests)r, %(root)r, %(pkg)r]
+import bench
+import index_build_gpu as G
+dev = torch.device("cuda", 0)
+codes, contigs = bench.synth_genome(torch, dev, 20_000_003, 5, 0x5EED)
+lib = bench.load_lib()
+lib.bwamem_hip_set_device(0)
+h = codes.cpu().numpy()
+names = (ctypes.c_char_p * len(contigs))(*[n.encode() for n, _ in contigs])
+lens = (ctypes.c_int64 * len(contigs))(*[l for _, l in contigs])
+a, b = os.path.join(%(workdir)r, "bi_lib.img"), os.path.join(%(workdir)r, "bi_torch.img")
+assert lib.bwamem_hip_build_image(h.ctypes.data, int(h.size), len(contigs), names, lens, a.encode()) == 0
+G.write_image(b, G.build_pieces(codes), contigs)
+assert open(a, "rb").read() == open(b, "rb").read(), "images differ"
+print("build-image-ok")
+"""
+
+
+@pytest.mark.gpu
+def test_library_image_builder_matches_torch_builder(workdir):
+    """bwamem_hip_build_image (bench.py's index builder: threaded packing and counting on the host, image streamed to the file)
+    against the torch builder, byte for byte, on a 20 Mbp genome of odd length (past the threads' threshold, partial last pac
+    byte).  Own process: torch has to initialise HIP before the library does."""
+    import subprocess
+    code = BUILD_IMAGE_CODE % dict(tests=os.path.join(B.ROOT, "tests"), root=B.ROOT, pkg=B.PKG, workdir=workdir)
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "build-image-ok" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
