@@ -22,6 +22,7 @@
 #include <thread>
 #include <atomic>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 #include <deque>
@@ -37,19 +38,37 @@
     fprintf(stderr, "[bwamem_hip] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return false; } } while (0)
 
 // ------------------------------------------------------------------------------------------
+// A device allocation owned by its scope.  Freed on the device current at destruction: owners are destroyed after
+// hipSetDevice(ix->device) (destroy_replica, bwamem_hip_batch_free, the paired-end call's owners).
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); std::swap(p, o.p); std::swap(bytes, o.bytes); } return *this; }
+    ~DevBuf() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     bool ensure(size_t n) {
         if (n <= bytes) return true;
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        reset();
         n += n / 8 + 256;
         hipError_t e = hipMalloc(&p, n);
         if (e != hipSuccess) { fprintf(stderr, "[bwamem_hip] hipMalloc(%zu) failed: %s\n", n, hipGetErrorString(e)); p = nullptr; return false; }
         bytes = n;
         return true;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     template <typename T> T* as() const { return (T*)p; }
+};
+
+// The threads of one scope, joined when it ends on every path (a joinable std::thread destroyed by a throw would call
+// std::terminate).  On such an early exit wake() runs first, so that threads parked on a condition variable see the failure.
+struct ThreadGroup {
+    std::vector<std::thread> th;
+    std::function<void()> wake;
+    explicit ThreadGroup(std::function<void()> wake_ = nullptr) : wake(std::move(wake_)) {}
+    template <typename... A> void spawn(A&&... a) { th.emplace_back(std::forward<A>(a)...); }
+    void join() { for (std::thread& t : th) if (t.joinable()) t.join(); th.clear(); }
+    ~ThreadGroup() { if (!th.empty() && wake) wake(); join(); }
 };
 
 struct Stats {
@@ -95,8 +114,9 @@ struct Workspace {
     int dev_lds = 0;                                  // LDS per workgroup of the device this workspace lives on
     DevBuf scan_tmp, packed, order;                        // block sums of the multi-block scan; the tile's packed records on their way to the host
     DevBuf pe_dir, pe_is, pe_caps, pe_reg_off2, pe_regs2, pe_ints2, pe_vpool, pe_scratch, pe_states, pe_rescue[3];   // paired-end stages
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;                     // owned
     std::vector<Timed> timed;
+    ~Workspace() { if (stream) (void)hipStreamDestroy(stream); }
 
     // with_seed = false: the tile takes its interval lists from a SeedStore (single-end path) and needs no seeding arrays
     bool ensure_reads(const MemOpt& opt, int T_, int L_, int intv_cap_, int out_cap_, int64_t post_per_read_, bool with_seed = true) {
@@ -128,16 +148,10 @@ struct Workspace {
             && chain_store.ensure(s * sizeof(Chain)) && bt_nodes.ensure((s / 4 + 3 * (size_t)T + 16) * BT_NODE_INTS * 4) && srt.ensure(s * 8)
             && regs.ensure(s * sizeof(AlnReg));
     }
-    void release() {
-        DevBuf* all[] = { &intv, &n_intv, &smem, &l_rep, &n_seeds, &seed_off, &intv_seed_off, &seeds, &seed_rid, &cseeds, &chains,
-                          &chain_store, &n_chains, &bt_nodes, &srt, &regs, &n_regs, &out, &out_len, &out_off, &post, &err, &cnt, &dp_rows,
-                          &jobs, &job_out, &job_cig, &job_cnt, &zpool, &zslabs, &pe_dir, &pe_is, &pe_caps, &pe_reg_off2, &pe_regs2, &pe_ints2, &pe_vpool, &pe_scratch, &pe_states,
-                          &pe_rescue[0], &pe_rescue[1], &pe_rescue[2], &scan_tmp, &packed, &order };
-        for (DevBuf* b : all) b->release();
-        if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
-    }
-    TileView view() const {
+    // the workspace's buffers as seen by the kernels of a tile of T reads of at most L bases, the first numbered read_id0
+    TileView view(int T_, int L_, int64_t read_id0, uint8_t* seq, const int64_t* seq_off) const {
         TileView tv; memset(&tv, 0, sizeof tv);
+        tv.n_reads = T_; tv.max_len = L_; tv.read_id0 = read_id0; tv.seq = seq; tv.seq_off = seq_off;
         tv.intv_cap = intv_cap; tv.intv = intv.as<Intv>(); tv.n_intv = n_intv.as<int32_t>();
         tv.smem_scratch = smem.as<Intv>(); tv.smem_cap = smem_cap; tv.l_rep = l_rep.as<int32_t>();
         tv.n_seeds = n_seeds.as<int32_t>(); tv.seed_off = seed_off.as<int64_t>(); tv.intv_seed_off = intv_seed_off.as<int32_t>();
@@ -169,7 +183,6 @@ struct SeedStore {
         return intv.ensure(reads * cap * sizeof(Intv)) && n_intv.ensure(reads * 4) && intv_seed_off.ensure(reads * cap * 4)
             && n_seeds.ensure(reads * 4) && l_rep.ensure(reads * 4);
     }
-    void release() { intv.release(); n_intv.release(); intv_seed_off.release(); n_seeds.release(); l_rep.release(); }
 };
 
 // A stretch of a request that jnibwa_createAlignments streams to the device while the first stretches are already being
@@ -177,7 +190,8 @@ struct SeedStore {
 // The buffers belong to the index and are reused by the next call (calls on one index are serialised).
 struct ReqBuf {
     DevBuf seq, off, tmp;
-    int64_t* h_off = nullptr; size_t h_cap = 0;       // hipHostMalloc
+    int64_t* h_off = nullptr; size_t h_cap = 0;       // hipHostMalloc, owned
+    ~ReqBuf() { if (h_off) (void)hipHostFree(h_off); }
     bool ensure_host(size_t n) {
         if (n <= h_cap) return true;
         if (h_off) (void)hipHostFree(h_off);
@@ -187,7 +201,6 @@ struct ReqBuf {
         h_cap = n;
         return true;
     }
-    void release() { seq.release(); off.release(); tmp.release(); if (h_off) (void)hipHostFree(h_off); h_off = nullptr; h_cap = 0; }
 };
 
 // What the tiles of earlier calls needed, per read, shared by all workspaces of an index: a tile is re-run when one of its
@@ -237,20 +250,26 @@ struct bwaidx_s {
     PairTab pair_tab;               // insert-size score terms of the running paired-end call (build_pair_tab)
     std::mutex mu;                  // one call at a time per index/device
     Workspace ws;
-    std::vector<Workspace*> extra_ws;   // further tiles in flight (one stream + host thread each)
+    std::vector<std::unique_ptr<Workspace>> extra_ws;   // further tiles in flight (one stream + host thread each)
     Workspace seed_ws;                  // stream, flags and spill area of the seeding stage (single-end path)
     SeedStore seed_store[SEED_STORES_MAX];   // a ring: chunk c + n is seeded while the tiles of chunk c run (n = seed_stores() - 1)
     CapHints hints;
-    std::vector<ReqBuf*> req_bufs;      // request stretches of a streamed call (jnibwa_createAlignments)
-    hipStream_t up_stream = nullptr;    // their uploads
+    std::vector<std::unique_ptr<ReqBuf>> req_bufs;      // request stretches of a streamed call (jnibwa_createAlignments)
+    hipStream_t up_stream = nullptr;    // their uploads (owned)
     // One handle, several devices (jnibwa_openIndex, BWAMEM_HIP_DEVICES): the handle is the replica on the first device and
     // owns the others, each a bwaidx_s of its own (index, workspaces, hints) over the same mapped image.
     std::vector<bwaidx_s*> peers;
     std::atomic<uint32_t> next_replica{0};   // small calls take the replicas in turn
     std::mutex split_mu;                     // one call at a time is cut across all replicas (its shards wait for each other while holding their replicas)
+    ~bwaidx_s() { if (up_stream) (void)hipStreamDestroy(up_stream); }
 };
 
 struct TileOut { uint8_t* d = nullptr; size_t bytes = 0; bool owned = false; };
+
+// A tile of a paired-end call between its two phases (regions per read, in HBM), and what phase 1 of a call leaves behind
+// for phase 2.  (A single-pass call frees each tile's regions as soon as its phase 2 is done: pe_begin.)
+struct PeTile { uint32_t r0 = 0; int T = 0, L = 0; uint8_t* seq = nullptr; const int64_t* seq_off = nullptr; DevBuf n_regs, regs, reg_off; int64_t n_regs_total = 0; std::vector<int8_t> cand_dir; std::vector<int64_t> cand_is; };
+struct PeCall { std::deque<PeTile> tiles; int64_t read_id0 = 0; };
 
 // Where the packed records of the tiles go.  Tiles finish out of order on their workers but the response is the
 // concatenation in read order, so a tile learns its offset once every earlier tile has announced its size.
@@ -331,7 +350,7 @@ struct bwamem_batch_s {
     std::deque<TileOut> tiles;
     OutSink sink;
     size_t result_bytes = 0;
-    struct PeCall* pe = nullptr;    // paired-end call split in two steps (bwamem_hip_batch_pe_begin / _finish): phase-1 products kept in HBM
+    std::unique_ptr<PeCall> pe;     // paired-end call split in two steps (bwamem_hip_batch_pe_begin / _finish): phase-1 products kept in HBM
 };
 
 static const int LOG_TAB_N = 1 << 20;
@@ -346,12 +365,11 @@ static bool upload_index(bwaidx_s* ix)
         DevBuf tmp;
         size_t bwt_bytes = ((size_t)h.bwt_size * 4 + 255) & ~(size_t)63;
         const uint64_t n_blocks = (h.seq_len + 63) / 64 + 1;
-        if (!tmp.ensure(bwt_bytes) || !ix->d_occ.ensure((size_t)n_blocks * 32 + 64)) { tmp.release(); return false; }
+        if (!tmp.ensure(bwt_bytes) || !ix->d_occ.ensure((size_t)n_blocks * 32 + 64)) return false;
         HIP_OK(hipMemset(tmp.p, 0, tmp.bytes));
         HIP_OK(hipMemcpy(tmp.p, h.bwt, (size_t)h.bwt_size * 4, hipMemcpyHostToDevice));
         launch_build_occ64(0, tmp.as<uint32_t>(), n_blocks, ix->d_occ.as<uint4>());
         HIP_OK(hipDeviceSynchronize());
-        tmp.release();
     }
     if (!ix->d_pac.ensure((size_t)(h.l_pac / 4 + 1) + 16)) return false;
     HIP_OK(hipMemcpy(ix->d_pac.p, h.pac, (size_t)(h.l_pac / 4 + 1), hipMemcpyHostToDevice));
@@ -399,32 +417,16 @@ static bool upload_index(bwaidx_s* ix)
         while ((1 << d.sa_shift) < dense) ++d.sa_shift;
         const size_t n_kept = (size_t)(h.seq_len >> d.sa_shift) + 1;
         DevBuf src, flag;
-        if (!ix->d_sa_lo.ensure(n_kept * 4 + 64) || !ix->d_sa_hi.ensure(n_kept + 64) || !src.ensure((size_t)h.n_sa * 8) || !flag.ensure(64)) { src.release(); flag.release(); return false; }
+        if (!ix->d_sa_lo.ensure(n_kept * 4 + 64) || !ix->d_sa_hi.ensure(n_kept + 64) || !src.ensure((size_t)h.n_sa * 8) || !flag.ensure(64)) return false;
         d.sa_lo = ix->d_sa_lo.as<uint32_t>(); d.sa_hi = ix->d_sa_hi.as<uint8_t>();
         int32_t bad = 1;
         if (hipMemcpy(src.p, h.sa, (size_t)h.n_sa * 8, hipMemcpyHostToDevice) == hipSuccess && hipMemset(flag.p, 0, 64) == hipSuccess) {
             launch_sa_densify(0, d, src.as<uint64_t>(), h.n_sa, h.sa_intv, ix->d_sa_lo.as<uint32_t>(), ix->d_sa_hi.as<uint8_t>(), flag.as<int32_t>());
             if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&bad, flag.p, 4, hipMemcpyDeviceToHost) != hipSuccess) bad = 1;
         }
-        src.release(); flag.release();
         if (bad) { fprintf(stderr, "[bwamem_hip] suffix array densification failed\n"); return false; }
     }
     return true;
-}
-
-static void free_index(bwaidx_s* ix)
-{
-    (void)hipSetDevice(ix->device);
-    DevBuf* all[] = { &ix->d_occ, &ix->d_sa_lo, &ix->d_sa_hi, &ix->d_pac, &ix->d_ann_off, &ix->d_ann_len, &ix->d_ann_alt, &ix->d_name_off, &ix->d_names, &ix->d_log, &ix->d_ptab };
-    for (DevBuf* b : all) b->release();
-    ix->ws.release();
-    ix->seed_ws.release();
-    for (SeedStore& st : ix->seed_store) st.release();
-    for (Workspace* w : ix->extra_ws) { w->release(); delete w; }
-    ix->extra_ws.clear();
-    for (ReqBuf* r : ix->req_bufs) { r->release(); delete r; }
-    ix->req_bufs.clear();
-    if (ix->up_stream) { (void)hipStreamDestroy(ix->up_stream); ix->up_stream = nullptr; }
 }
 
 // ------------------------------------------------------------------------------------------ roctx ranges
@@ -736,9 +738,7 @@ static bool seed_chunk(bwaidx_s* ix, const MemOpt& opt, const SeedChunk& ch, See
 // a tile's view of its reads and of its slice of the chunk's interval lists
 static TileView tile_view(const Workspace& ws, const TileSpec& spec, int64_t read_id0, const SeedStore& seeds_of_chunk, uint32_t chunk_r0)
 {
-    TileView v = ws.view();
-    v.n_reads = (int)(spec.r1 - spec.r0); v.max_len = spec.L; v.read_id0 = read_id0 + spec.r0;
-    v.seq = spec.seq; v.seq_off = spec.seq_off;
+    TileView v = ws.view((int)(spec.r1 - spec.r0), spec.L, read_id0 + spec.r0, spec.seq, spec.seq_off);
     const size_t at = (size_t)(spec.r0 - chunk_r0);
     v.intv_cap = seeds_of_chunk.cap;
     v.intv = seeds_of_chunk.intv.as<Intv>() + at * seeds_of_chunk.cap;
@@ -784,6 +784,59 @@ static bool emit_tile(Workspace& ws, bwamem_batch_s* b, size_t tile_index, const
     return true;
 }
 
+// The front of a tile, the same for a single-end tile and phase 1 of a paired-end one: the seed-count scan and the read order,
+// the seed occurrences read back (they size the seed buffers: tv is rebuilt when those grow), SA lookup, chaining, seed
+// re-scoring for long reads, extension and the first post stage.  clear_jobs: also zero the job counter (single-end; phase 1
+// has not sized the job buffers).  rescore_full: size the re-scoring list for every seed occurrence at once.
+static bool tile_front(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, const TileSpec& spec, int64_t read_id0, const SeedStore& seeds_of_chunk,
+                       uint32_t chunk_r0, bool clear_jobs, bool rescore_full, TileView& tv)
+{
+    const int T = (int)(spec.r1 - spec.r0);
+    tv = tile_view(ws, spec, read_id0, seeds_of_chunk, chunk_r0);
+    HIP_OK(hipMemsetAsync(ws.err.p, 0, 64, ws.stream));
+    HIP_OK(hipMemsetAsync(ws.cnt.p, 0, sizeof(DevCounters), ws.stream));
+    if (clear_jobs) HIP_OK(hipMemsetAsync(ws.job_cnt.p, 0, 64, ws.stream));
+    TIMED(ws, K_OTHER, launch_scan(ws.stream, tv.n_seeds, tv.seed_off, T, ws.scan_tmp.as<int64_t>()));
+    if (tv.order) TIMED(ws, K_OTHER, launch_order(ws.stream, tv.n_seeds, T, ws.order.as<int32_t>(), ws.order.as<int32_t>() + 64));
+    int64_t n_occ = 0;
+    HIP_OK(hipMemcpyAsync(&n_occ, tv.seed_off + T, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
+    ix->hints.saw_seeds(T, n_occ);
+    if (n_occ > ws.seed_cap) {
+        if (!ws.ensure_seeds(n_occ + n_occ / 4)) return false;
+        tv = tile_view(ws, spec, read_id0, seeds_of_chunk, chunk_r0);
+    }
+    TIMED(ws, K_SA, launch_sa(ws.stream, ix->d, opt, tv, n_occ));
+    TIMED(ws, K_CHAIN, launch_chain(ws.stream, ix->d, opt, tv, ws.chain_store.as<Chain>()));
+    if (rescore_needed(opt, tv)) {                     // long reads: seed re-scoring jobs (at most one per seed occurrence)
+        if (n_occ + 16 > 0x7fffffff) { fprintf(stderr, "[bwamem_hip] tile with more than 2^31 seed occurrences\n"); return false; }
+        // one job per seed occurrence at most, so n_occ slots always fit; BWAMEM_HIP_RESCORE_CAP0 (tests) makes the first
+        // attempt too small: the plan kernel then voids the list and the tile is run again with the full size
+        int rc = (int)(n_occ + 16);
+        if (!rescore_full) {
+            static const int cap0 = []{ const char* e = getenv("BWAMEM_HIP_RESCORE_CAP0"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
+            if (cap0) rc = cap0;
+        }
+        if (!(ws.pe_rescue[0].ensure(pe_rescue_bytes(0, rc)) && ws.pe_rescue[1].ensure(pe_rescue_bytes(1, rc)) && ws.pe_rescue[2].ensure((size_t)T * 8 + 64))) return false;
+        TIMED(ws, K_CHAIN, launch_rescore(ws.stream, ix->d, opt, tv, ws.pe_rescue[0].p, ws.pe_rescue[1].p, ws.pe_rescue[2].as<int32_t>() + 16, ws.pe_rescue[2].as<int32_t>(), rc));
+    }
+    TIMED(ws, K_EXTEND, launch_extend(ws.stream, ix->d, opt, tv));
+    if (getenv("BWAMEM_HIP_DUMP") && T <= 64) debug_dump(ws, tv, T);
+    TIMED(ws, K_POST, launch_post1(ws.stream, ix->d, opt, tv));
+    return true;
+}
+
+// the global alignments with traceback of the tile's n_jobs DP jobs (k_gcigar), into the workspace's job buffers
+static bool run_gcigar(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, const TileView& tv, int n_jobs)
+{
+    ws.zslab_bytes = gcigar_slab_bytes(opt, tv.max_len);
+    if (ws.zslab_bytes && !ws.zslabs.ensure(ws.zslab_bytes * (size_t)gcigar_slab_grid(ix->d, 1 << 30))) return false;
+    TIMED(ws, K_FINAL, launch_gcigar(ws.stream, ix->d, opt, tv, n_jobs, ws.jobs.p, ws.job_out.p, ws.job_cig.as<uint32_t>(), ws.job_cig_cap,
+                                     ws.zpool.as<uint8_t>(), (unsigned long long)ws.zpool_cap, (unsigned long long*)(ws.job_cnt.as<int32_t>() + 2),
+                                     ws.zslabs.as<uint8_t>(), ws.zslab_bytes, ws.job_cnt.as<int32_t>() + 4));
+    return true;
+}
+
 // one single-end tile, start to packed response, on the workspace's own stream
 static bool run_tile_se(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, bwamem_batch_s* b, int64_t read_id0, size_t tile_index, const TileSpec& spec,
                         TileOut& to, const SeedStore& seeds_of_chunk, uint32_t chunk_r0, int& out_cap)
@@ -806,34 +859,8 @@ static bool run_tile_se(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, bwamem_b
             if (gcigar_slab_bytes(opt, L)) zdef = std::min(zdef, (size_t)1 << 30);          // long reads: the wave form's matrices live in its slabs
             if (!ws.ensure_jobs(jc, 4 * L + 16, std::max(zpool_hint, (size_t)((double)zdef * zmult)))) return false;
         }
-        TileView tv = tile_view(ws, spec, read_id0, seeds_of_chunk, chunk_r0);
-        HIP_OK(hipMemsetAsync(ws.err.p, 0, 64, ws.stream));
-        HIP_OK(hipMemsetAsync(ws.cnt.p, 0, sizeof(DevCounters), ws.stream));
-        HIP_OK(hipMemsetAsync(ws.job_cnt.p, 0, 64, ws.stream));
-        TIMED(ws, K_OTHER, launch_scan(ws.stream, tv.n_seeds, tv.seed_off, T, ws.scan_tmp.as<int64_t>()));
-        if (tv.order) TIMED(ws, K_OTHER, launch_order(ws.stream, tv.n_seeds, T, ws.order.as<int32_t>(), ws.order.as<int32_t>() + 64));
-        int64_t n_occ = 0; int32_t err = 0; int32_t errv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        HIP_OK(hipMemcpyAsync(&n_occ, tv.seed_off + T, 8, hipMemcpyDeviceToHost, ws.stream));
-        HIP_OK(hipStreamSynchronize(ws.stream));
-        ix->hints.saw_seeds(T, n_occ);
-        if (n_occ > ws.seed_cap) {
-            if (!ws.ensure_seeds(n_occ + n_occ / 4)) return false;
-            tv = tile_view(ws, spec, read_id0, seeds_of_chunk, chunk_r0);
-        }
-        TIMED(ws, K_SA, launch_sa(ws.stream, ix->d, opt, tv, n_occ));
-        TIMED(ws, K_CHAIN, launch_chain(ws.stream, ix->d, opt, tv, ws.chain_store.as<Chain>()));
-        if (rescore_needed(opt, tv)) {                     // long reads: seed re-scoring jobs (at most one per seed occurrence)
-            if (n_occ + 16 > 0x7fffffff) { fprintf(stderr, "[bwamem_hip] tile with more than 2^31 seed occurrences\n"); return false; }
-            // one job per seed occurrence at most, so n_occ slots always fit; BWAMEM_HIP_RESCORE_CAP0 (tests) makes the first
-            // attempt too small: the plan kernel then voids the list and the tile is run again with the full size
-            static const int cap0 = []{ const char* e = getenv("BWAMEM_HIP_RESCORE_CAP0"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
-            const int rc = cap0 && !rescore_full ? cap0 : (int)(n_occ + 16);
-            if (!(ws.pe_rescue[0].ensure(pe_rescue_bytes(0, rc)) && ws.pe_rescue[1].ensure(pe_rescue_bytes(1, rc)) && ws.pe_rescue[2].ensure((size_t)T * 8 + 64))) return false;
-            TIMED(ws, K_CHAIN, launch_rescore(ws.stream, ix->d, opt, tv, ws.pe_rescue[0].p, ws.pe_rescue[1].p, ws.pe_rescue[2].as<int32_t>() + 16, ws.pe_rescue[2].as<int32_t>(), rc));
-        }
-        TIMED(ws, K_EXTEND, launch_extend(ws.stream, ix->d, opt, tv));
-        if (getenv("BWAMEM_HIP_DUMP") && T <= 64) debug_dump(ws, tv, T);
-        TIMED(ws, K_POST, launch_post1(ws.stream, ix->d, opt, tv));
+        TileView tv;
+        if (!tile_front(ix, ws, opt, spec, read_id0, seeds_of_chunk, chunk_r0, true, rescore_full, tv)) return false;
         if (L > 1000) {
             // long reads: regions per read vary by orders of magnitude, and a tile re-run costs seconds.  Every job is a region,
             // so the region count (known now) bounds the job list: size it before the jobs are listed instead of retrying
@@ -852,20 +879,17 @@ static bool run_tile_se(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, bwamem_b
         HIP_OK(hipMemcpyAsync(&n_jobs, tv.job_cnt, 4, hipMemcpyDeviceToHost, ws.stream));
         HIP_OK(hipStreamSynchronize(ws.stream));
         if (n_jobs > ws.job_cap) { job_cap_hint = n_jobs + n_jobs / 4; { std::lock_guard<std::mutex> lk(g_stats.mu); ++g_stats.s.n_retries; } continue; }
-        ws.zslab_bytes = gcigar_slab_bytes(opt, L);
-        if (ws.zslab_bytes && !ws.zslabs.ensure(ws.zslab_bytes * (size_t)gcigar_slab_grid(ix->d, 1 << 30))) return false;
-        TIMED(ws, K_FINAL, launch_gcigar(ws.stream, ix->d, opt, tv, n_jobs, ws.jobs.p, ws.job_out.p, ws.job_cig.as<uint32_t>(), ws.job_cig_cap,
-                                         ws.zpool.as<uint8_t>(), (unsigned long long)ws.zpool_cap, (unsigned long long*)(ws.job_cnt.as<int32_t>() + 2),
-                                         ws.zslabs.as<uint8_t>(), ws.zslab_bytes, ws.job_cnt.as<int32_t>() + 4));
+        if (!run_gcigar(ix, ws, opt, tv, n_jobs)) return false;
         TIMED(ws, K_FINAL, launch_final_se(ws.stream, ix->d, opt, tv, ws.job_out.p, ws.job_cig.as<uint32_t>(), ws.job_cig_cap));
         TIMED(ws, K_OTHER, launch_scan(ws.stream, tv.out_len, tv.out_off, T, ws.scan_tmp.as<int64_t>()));
         int64_t out_total = 0;
         DevCounters hc;
+        int32_t errv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         HIP_OK(hipMemcpyAsync(&out_total, tv.out_off + T, 8, hipMemcpyDeviceToHost, ws.stream));
         HIP_OK(hipMemcpyAsync(&hc, tv.cnt, sizeof hc, hipMemcpyDeviceToHost, ws.stream));
         HIP_OK(hipMemcpyAsync(errv, tv.err, sizeof errv, hipMemcpyDeviceToHost, ws.stream));
         HIP_OK(hipStreamSynchronize(ws.stream));
-        err = errv[0];
+        const int32_t err = errv[0];
         if (tv.debug & 0x2000) fprintf(stderr, "[bwamem_hip] global alignment, Mclk summed over waves: rows %.1f tile staging %.1f walk %.1f end %.1f | jobs %d\n", hc.dbg[5] / 1e6, hc.dbg[6] / 1e6, hc.dbg[7] / 1e6, hc.dbg[8] / 1e6, n_jobs);
         if (err) {
             { std::lock_guard<std::mutex> lk(g_stats.mu); ++g_stats.s.n_retries; }
@@ -905,6 +929,9 @@ struct CallPipe {
     void fail() { { std::lock_guard<std::mutex> lk(mu); failed = true; } cv.notify_all(); }
 };
 
+// reads per seeding chunk at most (BWAMEM_HIP_SEED_CHUNK), and per request stretch that a streamed call uploads at once
+static uint32_t seed_chunk_reads() { const char* e = getenv("BWAMEM_HIP_SEED_CHUNK"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 2097152u; }
+
 // Seeding chunks: runs of consecutive tiles.  k_seed cannot finish before its slowest read has (one lane walks one read),
 // so a launch over one tile spends much of its time in a thin tail; over a few million reads the queue keeps the lanes fed
 // for most of the launch.  The first chunks are small (one tile, then two, ...) so that the tile workers start early.
@@ -918,8 +945,7 @@ static void append_stretch(CallPipe& pp, const ReqChunk& rc, const MemOpt& opt, 
                                             // hide that better than larger ones amortise it (human-like genome, 4 M reads: 0.45 M reads/s with twice the reads per tile, 0.69 M without)
     std::vector<TileSpec> tiles;
     plan_tiles(rc, opt, even, false, tile_scale, tiles);
-    const char* e = getenv("BWAMEM_HIP_SEED_CHUNK");
-    const uint32_t chunk_reads = e && atoi(e) > 0 ? (uint32_t)atoi(e) : 2097152u;
+    const uint32_t chunk_reads = seed_chunk_reads();
     const char* eg = getenv("BWAMEM_HIP_SEED_GB");
     const int64_t budget = (int64_t)(eg && atoi(eg) > 0 ? atoi(eg) : 16) << 30;     // per interval store
     std::lock_guard<std::mutex> lk(pp.mu);
@@ -984,8 +1010,7 @@ static bool produce_streamed(bwaidx_s* ix, CallPipe& pp, bwamem_batch_s* b, cons
     if (!ix->up_stream) HIP_OK(hipStreamCreateWithFlags(&ix->up_stream, hipStreamNonBlocking));
     hipStream_t st = ix->up_stream;
     const uint32_t max_T = max_tile_reads(even, 1);
-    const char* e = getenv("BWAMEM_HIP_SEED_CHUNK");
-    const uint64_t chunk_reads = e && atoi(e) > 0 ? (uint64_t)atoi(e) : 2097152u;
+    const uint64_t chunk_reads = seed_chunk_reads();
     const char* eb = getenv("BWAMEM_HIP_UPLOAD_BYTES");
     const size_t max_bytes = eb && atoll(eb) > 0 ? (size_t)atoll(eb) : (size_t)384 << 20;
     const char* p = b->h_payload;
@@ -1002,7 +1027,7 @@ static bool produce_streamed(bwaidx_s* ix, CallPipe& pp, bwamem_batch_s* b, cons
         if (even && (got & 1) && r + got < b->n_reads) { uint64_t one = 0; end = scan_reads(end, 1, (size_t)-1, &one); got += one; }   // a pair is never split
         const size_t nbytes = (size_t)(end - p);
         if (nbytes >= ((size_t)1 << 40)) { fprintf(stderr, "[bwamem_hip] request stretch too large\n"); return false; }
-        if (k >= ix->req_bufs.size()) ix->req_bufs.push_back(new ReqBuf());
+        if (k >= ix->req_bufs.size()) ix->req_bufs.push_back(std::make_unique<ReqBuf>());
         ReqBuf& rb = *ix->req_bufs[k];
         if (!rb.seq.ensure(nbytes + 64) || !rb.off.ensure((got + 2) * 8 + 16) || !rb.tmp.ensure(nul_tmp_bytes((int64_t)nbytes)) || !rb.ensure_host(got + 2)) return false;
         int64_t* d_found = rb.off.as<int64_t>() + got + 1;           // one spare slot behind the offsets
@@ -1025,14 +1050,34 @@ static bool produce_streamed(bwaidx_s* ix, CallPipe& pp, bwamem_batch_s* b, cons
     return true;
 }
 
+// tiles in flight at once (BWAMEM_HIP_STREAMS): one worker thread, stream and workspace each
+static int tile_streams() { const char* e = getenv("BWAMEM_HIP_STREAMS"); return e ? atoi(e) : 4; }
+
+// The tile workers of a call: n of them, each with a workspace of the index -- worker 0 on the calling thread with ix->ws, the
+// others on threads of their own with ix->extra_ws (grown to n - 1).  Each sets its device, LDS size and stream, then runs
+// body; a worker whose setup or body fails, or that throws, calls fail().
+static void run_workers(bwaidx_s* ix, int n, const std::function<bool(Workspace&)>& body, const std::function<void()>& fail)
+{
+    while ((int)ix->extra_ws.size() < n - 1) ix->extra_ws.push_back(std::make_unique<Workspace>());
+    auto worker = [&](int k) {
+        try {
+            Workspace& w = k == 0 ? ix->ws : *ix->extra_ws[k - 1];
+            w.dev_lds = ix->d.lds_bytes;
+            if (hipSetDevice(ix->device) != hipSuccess || (!w.stream && hipStreamCreate(&w.stream) != hipSuccess) || !body(w)) fail();
+        } catch (const std::exception& ex) { fprintf(stderr, "[bwamem_hip] %s\n", ex.what()); fail(); }
+    };
+    ThreadGroup th(fail);
+    for (int k = 1; k < n; ++k) th.spawn(worker, k);
+    worker(0);
+    th.join();
+}
+
 // Runs fn for every tile of the call (see CallPipe).  fn finds the interval lists of its tile in the store it is handed
 // (at offset r0 - chunk_r0).
 typedef std::function<bool(Workspace&, size_t, const TileSpec&, const SeedStore&, uint32_t)> TileFn;
 static bool run_pipeline(bwaidx_s* ix, const MemOpt& opt, bwamem_batch_s* b, bool even, CallPipe& pp, const TileFn& fn)
 {
-    const char* env_s = getenv("BWAMEM_HIP_STREAMS");
-    const int n_workers = std::max(1, env_s ? atoi(env_s) : 4);
-    while ((int)ix->extra_ws.size() < n_workers - 1) ix->extra_ws.push_back(new Workspace());
+    const int n_workers = std::max(1, tile_streams());
     // BWAMEM_HIP_SEED_AHEAD=0 serialises the seeding behind the tiles (isolated kernel timings)
     const bool seed_ahead = !(getenv("BWAMEM_HIP_SEED_AHEAD") && atoi(getenv("BWAMEM_HIP_SEED_AHEAD")) == 0);
     // interval stores in the ring (BWAMEM_HIP_SEED_STORES, 2 .. SEED_STORES_MAX): with two the seeding kernel waits for the tiles of the
@@ -1079,36 +1124,29 @@ static bool run_pipeline(bwaidx_s* ix, const MemOpt& opt, bwamem_batch_s* b, boo
             }
         } catch (const std::exception& ex) { fprintf(stderr, "[bwamem_hip] %s\n", ex.what()); fail(); }
     };
-    auto worker = [&](int k) {
-        try {
-            Workspace& w = k == 0 ? ix->ws : *ix->extra_ws[k - 1];
-            w.dev_lds = ix->d.lds_bytes;
-            if (hipSetDevice(ix->device) != hipSuccess) { fail(); return; }
-            if (!w.stream && hipStreamCreate(&w.stream) != hipSuccess) { fail(); return; }
-            for (;;) {
-                size_t i, c; TileSpec sp; uint32_t chunk_r0;
-                {
-                    std::unique_lock<std::mutex> lk(pp.mu);
-                    pp.cv.wait(lk, [&] { return pp.failed || pp.next_tile < pp.specs.size() || pp.produced_all; });
-                    if (pp.failed || pp.next_tile >= pp.specs.size()) break;
-                    i = pp.next_tile++; sp = pp.specs[i]; c = pp.chunk_of[i];
-                    pp.cv.wait(lk, [&] { return pp.failed || pp.chunks[c].state != 0; });
-                    if (pp.failed || pp.chunks[c].state < 0) break;
-                    chunk_r0 = pp.chunks[c].r0;
-                }
-                const bool ok = fn(w, i, sp, ix->seed_store[c % (size_t)n_stores], chunk_r0);
-                { std::lock_guard<std::mutex> lk(pp.mu); --pp.chunks[c].tiles_left; }
-                pp.cv.notify_all();
-                if (!ok) { fail(); break; }
+    auto take_tiles = [&](Workspace& w) {
+        for (;;) {
+            size_t i, c; TileSpec sp; uint32_t chunk_r0;
+            {
+                std::unique_lock<std::mutex> lk(pp.mu);
+                pp.cv.wait(lk, [&] { return pp.failed || pp.next_tile < pp.specs.size() || pp.produced_all; });
+                if (pp.failed || pp.next_tile >= pp.specs.size()) return true;
+                i = pp.next_tile++; sp = pp.specs[i]; c = pp.chunk_of[i];
+                pp.cv.wait(lk, [&] { return pp.failed || pp.chunks[c].state != 0; });
+                if (pp.failed || pp.chunks[c].state < 0) return true;
+                chunk_r0 = pp.chunks[c].r0;
             }
-        } catch (const std::exception& ex) { fprintf(stderr, "[bwamem_hip] %s\n", ex.what()); fail(); }
+            const bool ok = fn(w, i, sp, ix->seed_store[c % (size_t)n_stores], chunk_r0);
+            { std::lock_guard<std::mutex> lk(pp.mu); --pp.chunks[c].tiles_left; }
+            pp.cv.notify_all();
+            if (!ok) return false;
+        }
     };
-    std::vector<std::thread> th;
-    th.emplace_back(producer);
-    th.emplace_back(seeder);
-    for (int k = 1; k < n_workers; ++k) th.emplace_back(worker, k);
-    worker(0);
-    for (std::thread& t : th) t.join();
+    ThreadGroup th(fail);
+    th.spawn(producer);
+    th.spawn(seeder);
+    run_workers(ix, n_workers, take_tiles, fail);
+    th.join();
     return !pp.failed;
 }
 
@@ -1116,63 +1154,40 @@ static bool run_pipeline(bwaidx_s* ix, const MemOpt& opt, bwamem_batch_s* b, boo
 // Phase 1 (per tile, tiles in flight like single-end, seeding in chunks): seeds .. regions of every read, kept per tile,
 // and the per-pair insert-size candidates.  Then the batch-global statistics on the host (mem_pestat), unless the caller
 // supplied them.  Phase 2 (per tile, tiles in flight): mate rescue, pairing, DP jobs, records.
-struct PeTile { uint32_t r0 = 0; int T = 0, L = 0; uint8_t* seq = nullptr; const int64_t* seq_off = nullptr; DevBuf n_regs, regs, reg_off; int64_t n_regs_total = 0; std::vector<int8_t> cand_dir; std::vector<int64_t> cand_is; };
 
-#define PE_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fprintf(stderr, "[bwamem_hip] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e_), __FILE__, __LINE__); return false; } } while (0)
-#define PE_REQ(cond) do { if (!(cond)) return false; } while (0)
-
-static bool pe_phase1_tile(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, bwamem_batch_s* b, int64_t read_id0, const TileSpec& spec, PeTile* pt,
+static bool pe_phase1_tile(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, int64_t read_id0, const TileSpec& spec, PeTile* pt,
                            const SeedStore& seeds_of_chunk, uint32_t chunk_r0, bool want_cand)
 {
     RoctxRange rr("bwamem_hip:tile_pe_phase1");
-    const uint32_t r0 = spec.r0;
     const int T = (int)(spec.r1 - spec.r0), L = spec.L;
-    PE_REQ(ws.ensure_reads(opt, T, L, seeds_of_chunk.cap, ws.out_cap_hint, post_bytes_per_read(L, opt, false), false));
-    PE_REQ(ws.ensure_seeds(std::max<int64_t>(ws.seed_cap, (int64_t)T * 16)));
-    auto make_view = [&]() { return tile_view(ws, spec, read_id0, seeds_of_chunk, chunk_r0); };
-    TileView tv = make_view();
-    PE_OK(hipMemsetAsync(ws.err.p, 0, 64, ws.stream));
-    PE_OK(hipMemsetAsync(ws.cnt.p, 0, sizeof(DevCounters), ws.stream));
-    TIMED(ws, K_OTHER, launch_scan(ws.stream, tv.n_seeds, tv.seed_off, T, ws.scan_tmp.as<int64_t>()));
-    if (tv.order) TIMED(ws, K_OTHER, launch_order(ws.stream, tv.n_seeds, T, ws.order.as<int32_t>(), ws.order.as<int32_t>() + 64));
-    int64_t n_occ = 0; int32_t err = 0;
-    PE_OK(hipMemcpyAsync(&n_occ, tv.seed_off + T, 8, hipMemcpyDeviceToHost, ws.stream));
-    PE_OK(hipStreamSynchronize(ws.stream));
-    ix->hints.saw_seeds(T, n_occ);
-    if (n_occ > ws.seed_cap) { PE_REQ(ws.ensure_seeds(n_occ + n_occ / 4)); tv = make_view(); }
-    TIMED(ws, K_SA, launch_sa(ws.stream, ix->d, opt, tv, n_occ));
-    TIMED(ws, K_CHAIN, launch_chain(ws.stream, ix->d, opt, tv, ws.chain_store.as<Chain>()));
-    if (rescore_needed(opt, tv)) {                     // long reads: seed re-scoring jobs (at most one per seed occurrence)
-        if (n_occ + 16 > 0x7fffffff) { fprintf(stderr, "[bwamem_hip] tile with more than 2^31 seed occurrences\n"); return false; }
-        const int rc = (int)(n_occ + 16);                  // one job per seed occurrence at most: the list always fits (see run_tile_se)
-        if (!(ws.pe_rescue[0].ensure(pe_rescue_bytes(0, rc)) && ws.pe_rescue[1].ensure(pe_rescue_bytes(1, rc)) && ws.pe_rescue[2].ensure((size_t)T * 8 + 64))) return false;
-        TIMED(ws, K_CHAIN, launch_rescore(ws.stream, ix->d, opt, tv, ws.pe_rescue[0].p, ws.pe_rescue[1].p, ws.pe_rescue[2].as<int32_t>() + 16, ws.pe_rescue[2].as<int32_t>(), rc));
-    }
-    TIMED(ws, K_EXTEND, launch_extend(ws.stream, ix->d, opt, tv));
-    TIMED(ws, K_POST, launch_post1(ws.stream, ix->d, opt, tv));
-    pt->r0 = r0; pt->T = T; pt->L = L; pt->seq = spec.seq; pt->seq_off = spec.seq_off;
-    PE_REQ(pt->n_regs.ensure((size_t)T * 4) && pt->reg_off.ensure(((size_t)T + 1) * 8));
+    if (!ws.ensure_reads(opt, T, L, seeds_of_chunk.cap, ws.out_cap_hint, post_bytes_per_read(L, opt, false), false)) return false;
+    if (!ws.ensure_seeds(std::max<int64_t>(ws.seed_cap, (int64_t)T * 16))) return false;
+    TileView tv;
+    if (!tile_front(ix, ws, opt, spec, read_id0, seeds_of_chunk, chunk_r0, false, true, tv)) return false;
+    pt->r0 = spec.r0; pt->T = T; pt->L = L; pt->seq = spec.seq; pt->seq_off = spec.seq_off;
+    if (!(pt->n_regs.ensure((size_t)T * 4) && pt->reg_off.ensure(((size_t)T + 1) * 8))) return false;
     TIMED(ws, K_OTHER, launch_scan(ws.stream, tv.n_regs, pt->reg_off.as<int64_t>(), T, ws.scan_tmp.as<int64_t>()));
+    int32_t err = 0;
     DevCounters hc;
-    PE_OK(hipMemcpyAsync(&pt->n_regs_total, pt->reg_off.as<int64_t>() + T, 8, hipMemcpyDeviceToHost, ws.stream));
-    PE_OK(hipMemcpyAsync(&err, tv.err, 4, hipMemcpyDeviceToHost, ws.stream));
-    PE_OK(hipMemcpyAsync(&hc, tv.cnt, sizeof hc, hipMemcpyDeviceToHost, ws.stream));
-    PE_OK(hipStreamSynchronize(ws.stream));
+    HIP_OK(hipMemcpyAsync(&pt->n_regs_total, pt->reg_off.as<int64_t>() + T, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(&err, tv.err, 4, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(&hc, tv.cnt, sizeof hc, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
     if (err) { fprintf(stderr, "[bwamem_hip] device error flags %d in the paired-end phase 1\n", err); return false; }
-    PE_REQ(pt->regs.ensure((size_t)(pt->n_regs_total + 1) * sizeof(AlnReg)));
-    PE_OK(hipMemcpyAsync(pt->n_regs.p, tv.n_regs, (size_t)T * 4, hipMemcpyDeviceToDevice, ws.stream));
+    if (!pt->regs.ensure((size_t)(pt->n_regs_total + 1) * sizeof(AlnReg))) return false;
+    HIP_OK(hipMemcpyAsync(pt->n_regs.p, tv.n_regs, (size_t)T * 4, hipMemcpyDeviceToDevice, ws.stream));
     TIMED(ws, K_OTHER, launch_pe_copy_regs(ws.stream, tv, tv.regs, tv.seed_off, pt->regs.as<AlnReg>(), pt->reg_off.as<int64_t>(), tv.n_regs));
     if (want_cand) {
         const int np = T >> 1;
-        PE_REQ(ws.pe_dir.ensure((size_t)np + 8) && ws.pe_is.ensure((size_t)np * 8 + 8));
+        if (!(ws.pe_dir.ensure((size_t)np + 8) && ws.pe_is.ensure((size_t)np * 8 + 8))) return false;
         TIMED(ws, K_OTHER, launch_pestat_cand(ws.stream, ix->d, opt, tv, ws.pe_dir.as<int8_t>(), ws.pe_is.as<int64_t>()));
         pt->cand_dir.resize(np); pt->cand_is.resize(np);
         if (np) {
-            PE_OK(hipMemcpyAsync(pt->cand_dir.data(), ws.pe_dir.p, (size_t)np, hipMemcpyDeviceToHost, ws.stream));
-            PE_OK(hipMemcpyAsync(pt->cand_is.data(), ws.pe_is.p, (size_t)np * 8, hipMemcpyDeviceToHost, ws.stream));
+            HIP_OK(hipMemcpyAsync(pt->cand_dir.data(), ws.pe_dir.p, (size_t)np, hipMemcpyDeviceToHost, ws.stream));
+            HIP_OK(hipMemcpyAsync(pt->cand_is.data(), ws.pe_is.p, (size_t)np * 8, hipMemcpyDeviceToHost, ws.stream));
         }
     }
-    PE_OK(hipStreamSynchronize(ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
     {
         std::lock_guard<std::mutex> lk(g_stats.mu);
         g_stats.s.n_reads += T; g_stats.s.n_lf += hc.n_lf; g_stats.s.n_sa += hc.n_sa; g_stats.s.n_dp_cells += hc.n_dp_cells; ++g_stats.s.n_tiles;
@@ -1190,41 +1205,35 @@ static bool pe_phase2_tile(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, bwame
     size_t pe_zpool = 0;
     for (;;) {
         if (++attempts > 8) { fprintf(stderr, "[bwamem_hip] paired-end tile could not be sized\n"); return false; }
-        PE_REQ(ws.ensure_reads(opt, T, L, 0, ws.out_cap_hint, post_bytes_per_read(L, opt, false), false));
-        TileView tv = ws.view();
-        tv.n_reads = T; tv.max_len = L; tv.read_id0 = read_id0 + pt->r0;
-        tv.seq = pt->seq; tv.seq_off = pt->seq_off;
-        PE_OK(hipMemsetAsync(ws.err.p, 0, 64, ws.stream));
-        PE_OK(hipMemcpyAsync(tv.n_regs, pt->n_regs.p, (size_t)T * 4, hipMemcpyDeviceToDevice, ws.stream));
-        PE_REQ(ws.pe_caps.ensure((size_t)T * 4) && ws.pe_reg_off2.ensure(((size_t)T + 1) * 8));
+        if (!ws.ensure_reads(opt, T, L, 0, ws.out_cap_hint, post_bytes_per_read(L, opt, false), false)) return false;
+        TileView tv = ws.view(T, L, read_id0 + pt->r0, pt->seq, pt->seq_off);
+        HIP_OK(hipMemsetAsync(ws.err.p, 0, 64, ws.stream));
+        HIP_OK(hipMemcpyAsync(tv.n_regs, pt->n_regs.p, (size_t)T * 4, hipMemcpyDeviceToDevice, ws.stream));
+        if (!(ws.pe_caps.ensure((size_t)T * 4) && ws.pe_reg_off2.ensure(((size_t)T + 1) * 8))) return false;
         TIMED(ws, K_OTHER, launch_pe_caps(ws.stream, opt, tv, ws.pe_caps.as<int32_t>()));
         TIMED(ws, K_OTHER, launch_scan(ws.stream, ws.pe_caps.as<int32_t>(), ws.pe_reg_off2.as<int64_t>(), T, ws.scan_tmp.as<int64_t>()));
         int64_t tot = 0;
-        PE_OK(hipMemcpyAsync(&tot, ws.pe_reg_off2.as<int64_t>() + T, 8, hipMemcpyDeviceToHost, ws.stream));
-        PE_OK(hipStreamSynchronize(ws.stream));
+        HIP_OK(hipMemcpyAsync(&tot, ws.pe_reg_off2.as<int64_t>() + T, 8, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipStreamSynchronize(ws.stream));
         int span = 0;
         for (int d = 0; d < 4; ++d) if (!pes[d].failed) span = std::max(span, pes[d].high - pes[d].low);
         const int cap_h = L + 32, cap_b = (span + 2 * L) / 2 + 16;
         const int64_t per_pair = (((int64_t)16 * cap_h + (int64_t)8 * cap_b + (int64_t)2 * opt.max_matesw * sizeof(AlnReg) + (int64_t)16 * cap_u) + 63) & ~(int64_t)63;
-        PE_REQ(ws.pe_regs2.ensure((size_t)(tot + 1) * sizeof(AlnReg)) && ws.pe_ints2.ensure((size_t)(tot + 1) * 8) && ws.pe_vpool.ensure((size_t)(tot + 2) * 16 + 64 + (size_t)(tot + 2) * 24)
-               && ws.pe_scratch.ensure((size_t)((T >> 1) + 1) * (size_t)per_pair));
+        if (!(ws.pe_regs2.ensure((size_t)(tot + 1) * sizeof(AlnReg)) && ws.pe_ints2.ensure((size_t)(tot + 1) * 8) && ws.pe_vpool.ensure((size_t)(tot + 2) * 16 + 64 + (size_t)(tot + 2) * 24)
+               && ws.pe_scratch.ensure((size_t)((T >> 1) + 1) * (size_t)per_pair))) return false;
         AlnReg* regs2 = ws.pe_regs2.as<AlnReg>(); int64_t* reg_off2 = ws.pe_reg_off2.as<int64_t>();
         TIMED(ws, K_OTHER, launch_pe_copy_regs(ws.stream, tv, pt->regs.as<AlnReg>(), pt->reg_off.as<int64_t>(), regs2, reg_off2, tv.n_regs));
         // pairing decisions and the list of regions whose CIGAR needs DP; the DP jobs; the records
         const int jc = std::max(pe_job_cap, std::max(1024, T / 2));
-        PE_REQ(ws.ensure_jobs(jc, 4 * L + 16, std::max(pe_zpool, (size_t)jc * (size_t)(2 * L + 64) * 20 + ((size_t)64 << 20))));
-        PE_REQ(ws.pe_states.ensure(pe_state_bytes(T)));
-        {   // the job buffers may have moved
-            TileView t2 = ws.view();
-            t2.n_reads = T; t2.max_len = L; t2.read_id0 = tv.read_id0; t2.seq = tv.seq; t2.seq_off = tv.seq_off;
-            tv = t2;
-        }
-        PE_OK(hipMemsetAsync(ws.job_cnt.p, 0, 64, ws.stream));
-        if (tv.debug & 0x2000) PE_OK(hipMemsetAsync(ws.cnt.p, 0, sizeof(DevCounters), ws.stream));
+        if (!ws.ensure_jobs(jc, 4 * L + 16, std::max(pe_zpool, (size_t)jc * (size_t)(2 * L + 64) * 20 + ((size_t)64 << 20)))) return false;
+        if (!ws.pe_states.ensure(pe_state_bytes(T))) return false;
+        tv = ws.view(T, L, tv.read_id0, tv.seq, tv.seq_off);              // (the job buffers may have moved)
+        HIP_OK(hipMemsetAsync(ws.job_cnt.p, 0, 64, ws.stream));
+        if (tv.debug & 0x2000) HIP_OK(hipMemsetAsync(ws.cnt.p, 0, sizeof(DevCounters), ws.stream));
         {   // rescue alignments: a few per cent of the pairs ask for one, pairs in repeats for many
             static const int floor0 = []{ const char* e = getenv("BWAMEM_HIP_PE_RESCUE_CAP0"); return e && atoi(e) > 0 ? atoi(e) : 4096; }();   // test knob: start small, take the resize path
             const int rc = std::max(pe_rescue_cap, floor0 < 4096 ? floor0 : std::max(4096, T / 8));
-            PE_REQ(ws.pe_rescue[0].ensure(pe_rescue_bytes(0, rc)) && ws.pe_rescue[1].ensure(pe_rescue_bytes(1, rc)) && ws.pe_rescue[2].ensure((size_t)(T / 2 + 1) * 12 + 64));   // header, first / count of each pair's rescue jobs, list of the heavy pairs
+            if (!(ws.pe_rescue[0].ensure(pe_rescue_bytes(0, rc)) && ws.pe_rescue[1].ensure(pe_rescue_bytes(1, rc)) && ws.pe_rescue[2].ensure((size_t)(T / 2 + 1) * 12 + 64))) return false;   // header, first / count of each pair's rescue jobs, list of the heavy pairs
             pe_rescue_cap = rc;
         }
         TIMED(ws, K_FINAL, launch_pe_pair(ws.stream, ix->d, opt, tv, regs2, reg_off2, tv.n_regs, ws.pe_ints2.as<int32_t>(), ws.pe_vpool.p, (char*)ws.pe_vpool.p + (((size_t)(tot + 2) * 16 + 63) & ~(size_t)63),
@@ -1232,13 +1241,13 @@ static bool pe_phase2_tile(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, bwame
                                           ws.pe_rescue[0].p, ws.pe_rescue[1].p, ws.pe_rescue[2].as<int32_t>() + 16, ws.pe_rescue[2].as<int32_t>() + 16 + (T / 2 + 1),
                                           ws.pe_rescue[2].as<int32_t>(), pe_rescue_cap));
         int32_t n_jobs = 0, err = 0, n_rescue = 0;
-        PE_OK(hipMemcpyAsync(&n_jobs, tv.job_cnt, 4, hipMemcpyDeviceToHost, ws.stream));
-        PE_OK(hipMemcpyAsync(&err, tv.err, 4, hipMemcpyDeviceToHost, ws.stream));
-        PE_OK(hipMemcpyAsync(&n_rescue, ws.pe_rescue[2].p, 4, hipMemcpyDeviceToHost, ws.stream));
-        PE_OK(hipStreamSynchronize(ws.stream));
+        HIP_OK(hipMemcpyAsync(&n_jobs, tv.job_cnt, 4, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipMemcpyAsync(&err, tv.err, 4, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipMemcpyAsync(&n_rescue, ws.pe_rescue[2].p, 4, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipStreamSynchronize(ws.stream));
         if (tv.debug & 0x2000) {
             DevCounters hc;
-            PE_OK(hipMemcpy(&hc, tv.cnt, sizeof hc, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(&hc, tv.cnt, sizeof hc, hipMemcpyDeviceToHost));
             fprintf(stderr, "[bwamem_hip] pairing stage, Mclk summed over waves: rescue %.1f mark_primary %.1f pair %.1f jobs %.1f | plan %.1f | rescue jobs %d\n",
                     hc.dbg[0] / 1e6, hc.dbg[1] / 1e6, hc.dbg[2] / 1e6, hc.dbg[3] / 1e6, hc.dbg[4] / 1e6, n_rescue);
         }
@@ -1250,37 +1259,22 @@ static bool pe_phase2_tile(bwaidx_s* ix, Workspace& ws, const MemOpt& opt, bwame
         {
             TileView tvj = tv;                              // the job kernels address a region as regs[seed_off[read] + index]
             tvj.regs = regs2; tvj.seed_off = reg_off2;
-            ws.zslab_bytes = gcigar_slab_bytes(opt, L);
-            PE_REQ(!ws.zslab_bytes || ws.zslabs.ensure(ws.zslab_bytes * (size_t)gcigar_slab_grid(ix->d, 1 << 30)));
-            TIMED(ws, K_FINAL, launch_gcigar(ws.stream, ix->d, opt, tvj, n_jobs, ws.jobs.p, ws.job_out.p, ws.job_cig.as<uint32_t>(), ws.job_cig_cap,
-                                             ws.zpool.as<uint8_t>(), (unsigned long long)ws.zpool_cap, (unsigned long long*)(ws.job_cnt.as<int32_t>() + 2),
-                                             ws.zslabs.as<uint8_t>(), ws.zslab_bytes, ws.job_cnt.as<int32_t>() + 4));
+            if (!run_gcigar(ix, ws, opt, tvj, n_jobs)) return false;
         }
         TIMED(ws, K_FINAL, launch_pe_out(ws.stream, ix->d, opt, tv, regs2, reg_off2, tv.n_regs, ws.pe_ints2.as<int32_t>(), pes, ws.pe_states.p,
                                          ws.job_out.p, ws.job_cig.as<uint32_t>(), ws.job_cig_cap));
         TIMED(ws, K_OTHER, launch_scan(ws.stream, tv.out_len, tv.out_off, T, ws.scan_tmp.as<int64_t>()));
         int64_t out_total = 0;
-        PE_OK(hipMemcpyAsync(&out_total, tv.out_off + T, 8, hipMemcpyDeviceToHost, ws.stream));
-        PE_OK(hipMemcpyAsync(&err, tv.err, 4, hipMemcpyDeviceToHost, ws.stream));
-        PE_OK(hipStreamSynchronize(ws.stream));
+        HIP_OK(hipMemcpyAsync(&out_total, tv.out_off + T, 8, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipMemcpyAsync(&err, tv.err, 4, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipStreamSynchronize(ws.stream));
         if (err & ERR_OUT_CAP) { ws.out_cap_hint *= 4; continue; }
         if (err & ERR_ZPOOL) { pe_zpool = std::max(pe_zpool * 4, ws.zpool_cap * 4); continue; }
         if (err) { fprintf(stderr, "[bwamem_hip] device error flags %d in the paired-end phase 2\n", err); return false; }
-        PE_REQ(emit_tile(ws, b, tile_index, tv, out_total, to));
+        if (!emit_tile(ws, b, tile_index, tv, out_total, to)) return false;
         timed_collect(ws);
         return true;
     }
-}
-#undef PE_OK
-#undef PE_REQ
-
-// what phase 1 of a paired-end call leaves behind for phase 2
-struct PeCall { std::deque<PeTile> tiles; int64_t read_id0 = 0; };
-static void pe_call_free(bwamem_batch_s* b)
-{
-    if (!b->pe) return;
-    for (PeTile& t : b->pe->tiles) { t.n_regs.release(); t.regs.release(); t.reg_off.release(); }
-    delete b->pe; b->pe = nullptr;
 }
 
 // phase 1 over all tiles (seeding .. regions per read).  The insert-size statistics are a property of the whole call,
@@ -1288,9 +1282,10 @@ static void pe_call_free(bwamem_batch_s* b)
 // supplies them (pes0) a tile goes straight on to phase 2 on the same worker and the call is a single pass
 static bool pe_begin(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes0, bwamem_batch_s* b, int64_t read_id0)
 {
-    pe_call_free(b);
+    b->pe.reset();
     if (pes0 && !build_pair_tab(ix, pes0)) return false;
-    PeCall* pc = b->pe = new PeCall();
+    PeCall* pc = new PeCall();
+    b->pe.reset(pc);
     pc->read_id0 = read_id0;
     CallPipe pp;
     pp.on_new_tiles = [&](size_t n) { pc->tiles.resize(pc->tiles.size() + n); b->tiles.resize(b->tiles.size() + n); b->sink.add_tiles(n); };
@@ -1298,15 +1293,15 @@ static bool pe_begin(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes0, bwa
             if (!read_length_ok(ix, spec.L)) return false;
             PeTile* pt; TileOut* to;
             { std::lock_guard<std::mutex> lk(pp.mu); pt = &pc->tiles[i]; to = &b->tiles[i]; }     // (the deques grow while tiles run; their elements stay put)
-            if (!pe_phase1_tile(ix, w, opt, b, read_id0, spec, pt, store, chunk_r0, pes0 == nullptr)) return false;
+            if (!pe_phase1_tile(ix, w, opt, read_id0, spec, pt, store, chunk_r0, pes0 == nullptr)) return false;
             if (!pes0) return true;
             const bool ok = pe_phase2_tile(ix, w, opt, b, read_id0, i, pt, pes0, *to);
-            pt->n_regs.release(); pt->regs.release(); pt->reg_off.release();
+            *pt = PeTile();                 // the tile's regions go back to HBM now, not at the end of the call
             return ok;
-        })) { pe_call_free(b); return false; }
+        })) { b->pe.reset(); return false; }
     if (pes0) {
         for (const TileOut& t : b->tiles) b->result_bytes += t.bytes;
-        pe_call_free(b);
+        b->pe.reset();
     }
     return true;
 }
@@ -1315,32 +1310,22 @@ static bool pe_begin(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes0, bwa
 static bool pe_finish(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes, bwamem_batch_s* b)
 {
     if (!b->pe) return false;
-    if (!build_pair_tab(ix, pes)) { pe_call_free(b); return false; }
+    if (!build_pair_tab(ix, pes)) { b->pe.reset(); return false; }
     std::deque<PeTile>& tiles = b->pe->tiles;
     const int64_t read_id0 = b->pe->read_id0;
-    const char* env_s = getenv("BWAMEM_HIP_STREAMS");
-    const int n_workers = std::max(1, std::min<int>((int)tiles.size(), env_s ? atoi(env_s) : 4));
-    while ((int)ix->extra_ws.size() < n_workers - 1) ix->extra_ws.push_back(new Workspace());
+    const int n_workers = std::max(1, std::min<int>((int)tiles.size(), tile_streams()));
     std::atomic<size_t> next(0);
     std::atomic<bool> failed(false);
-    auto worker = [&](int k) {
-        try {
-            Workspace& w = k == 0 ? ix->ws : *ix->extra_ws[k - 1];
-            w.dev_lds = ix->d.lds_bytes;
-            if (hipSetDevice(ix->device) != hipSuccess || (!w.stream && hipStreamCreate(&w.stream) != hipSuccess)) { failed = true; b->sink.abort(); return; }
-            while (!failed) {
-                const size_t i = next++;
-                if (i >= tiles.size()) break;
-                if (!pe_phase2_tile(ix, w, opt, b, read_id0, i, &tiles[i], pes, b->tiles[i])) { failed = true; b->sink.abort(); }
-            }
-        } catch (const std::exception& ex) { fprintf(stderr, "[bwamem_hip] %s\n", ex.what()); failed = true; b->sink.abort(); }
-    };
-    std::vector<std::thread> th;
-    for (int k = 1; k < n_workers; ++k) th.emplace_back(worker, k);
-    worker(0);
-    for (std::thread& t : th) t.join();
+    run_workers(ix, n_workers, [&](Workspace& w) {
+        while (!failed) {
+            const size_t i = next++;
+            if (i >= tiles.size()) break;
+            if (!pe_phase2_tile(ix, w, opt, b, read_id0, i, &tiles[i], pes, b->tiles[i])) return false;
+        }
+        return true;
+    }, [&] { failed = true; b->sink.abort(); });
     if (!failed) { for (const TileOut& t : b->tiles) b->result_bytes += t.bytes; b->sink.last_total = b->result_bytes; }
-    pe_call_free(b);
+    b->pe.reset();
     return !failed;
 }
 
@@ -1366,15 +1351,16 @@ static bool align_batch_pe(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes
     return pe_finish(ix, opt, pes, b);
 }
 
-// Tiles are independent, and every kernel of a tile ends in a tail of a few long-running reads; several tiles are
-// therefore kept in flight on separate HIP streams (one host thread + workspace each) so that one tile's tail
-// overlaps the next tile's bulk.
-// pe_step = 1: only phase 1 of a paired-end call (bwamem_hip_batch_pe_begin)
 static void release_tile_outputs(bwamem_batch_s* b)
 {
     for (TileOut& t : b->tiles) if (t.d && t.owned) (void)hipFree(t.d);
     b->tiles.clear(); b->result_bytes = 0;
 }
+
+// Tiles are independent, and every kernel of a tile ends in a tail of a few long-running reads; several tiles are
+// therefore kept in flight on separate HIP streams (one host thread + workspace each) so that one tile's tail
+// overlaps the next tile's bulk.
+// pe_step = 1: only phase 1 of a paired-end call (bwamem_hip_batch_pe_begin)
 
 static bool align_batch(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes, bwamem_batch_s* b, int64_t read_id0, int pe_step = 0)
 {
@@ -1382,7 +1368,7 @@ static bool align_batch(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes, b
     Workspace& ws = ix->ws;
     if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
     release_tile_outputs(b);
-    pe_call_free(b);
+    b->pe.reset();
     b->sink.begin_call(b->n_reads);
     if (b->n_reads == 0) return true;
     if (!b->h_payload) {                                   // resident batch: fresh working copy of the bases
@@ -1517,7 +1503,7 @@ static std::vector<int> index_devices()
     return v;
 }
 
-static void destroy_replica(bwaidx_s* ix) { free_index(ix); delete ix; }
+static void destroy_replica(bwaidx_s* ix) { (void)hipSetDevice(ix->device); delete ix; }     // (its HBM is freed on its device)
 
 bwaidx_t* jnibwa_openIndex(int fd)
 {
@@ -1527,32 +1513,33 @@ bwaidx_t* jnibwa_openIndex(int fd)
         void* mem = mmap(0, (size_t)st.st_size, PROT_READ, MAP_SHARED, fd, 0);
         close(fd);
         if (mem == MAP_FAILED) return 0;
-        const std::vector<int> devs = index_devices();
         std::vector<bwaidx_s*> reps;
-        std::vector<char> ok(devs.size(), 0);
-        for (size_t k = 0; k < devs.size(); ++k) {
-            bwaidx_s* ix = new bwaidx_s();
-            ix->mem = (uint8_t*)mem; ix->l_mem = (size_t)st.st_size; ix->mmapped = k == 0; ix->device = devs[k];
-            reps.push_back(ix);
-        }
-        auto load = [&](size_t k) {
-            try { bwaidx_s* ix = reps[k]; ok[k] = parse_index_image(ix->mem, ix->l_mem, ix->h) && ix->h.seq_len < (1ull << 37) && upload_index(ix); }   // 37-bit ranks: packed SMEM candidates
-            catch (...) { ok[k] = 0; }
-        };
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < reps.size(); ++k) th.emplace_back(load, k);      // every device loads from the one mapped image, side by side
-        load(0);
-        for (std::thread& t : th) t.join();
-        bool all = true;
-        for (char c : ok) all = all && c;
-        if (!all) {
-            fprintf(stderr, "[bwamem_hip] cannot open index image (malformed image or no usable HIP device)\n");
-            for (bwaidx_s* ix : reps) destroy_replica(ix);
-            munmap(mem, (size_t)st.st_size);
-            return 0;
-        }
-        for (size_t k = 1; k < reps.size(); ++k) reps[0]->peers.push_back(reps[k]);
-        return reps[0];
+        auto discard = [&] { for (bwaidx_s* ix : reps) destroy_replica(ix); munmap(mem, (size_t)st.st_size); };
+        try {
+            const std::vector<int> devs = index_devices();
+            std::vector<char> ok(devs.size(), 0);
+            reps.reserve(devs.size());
+            for (size_t k = 0; k < devs.size(); ++k) {
+                reps.push_back(new bwaidx_s());
+                bwaidx_s* ix = reps.back();
+                ix->mem = (uint8_t*)mem; ix->l_mem = (size_t)st.st_size; ix->mmapped = k == 0; ix->device = devs[k];
+            }
+            auto load = [&](size_t k) {
+                try { bwaidx_s* ix = reps[k]; ok[k] = parse_index_image(ix->mem, ix->l_mem, ix->h) && ix->h.seq_len < (1ull << 37) && upload_index(ix); }   // 37-bit ranks: packed SMEM candidates
+                catch (...) { ok[k] = 0; }
+            };
+            ThreadGroup th;
+            for (size_t k = 1; k < reps.size(); ++k) th.spawn(load, k);      // every device loads from the one mapped image, side by side
+            load(0);
+            th.join();
+            if (std::find(ok.begin(), ok.end(), 0) != ok.end()) {
+                fprintf(stderr, "[bwamem_hip] cannot open index image (malformed image or no usable HIP device)\n");
+                discard();
+                return 0;
+            }
+            for (size_t k = 1; k < reps.size(); ++k) reps[0]->peers.push_back(reps[k]);
+            return reps[0];
+        } catch (...) { discard(); throw; }         // (the loaders have been joined)
     });
 }
 
@@ -1627,18 +1614,19 @@ int bwamem_hip_index_unpack_pac(bwaidx_t* idx, int64_t start, int64_t n, void* d
     return hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -1;
 }
 
-// the request's strings (payload = pSeq + 4) with their offsets already known: device copies of both
-static bwamem_batch_s* batch_from_offsets(bwaidx_t* idx, const char* payload, uint32_t n_reads, std::vector<int64_t>&& off)
+// A batch resident in HBM: device copies of the request's n_bytes of strings (payload: host or device memory, as kind says)
+// and of their n_reads + 1 offsets, which must end at n_bytes.  what: the name of the failure on stderr.
+static bwamem_batch_s* resident_batch(bwaidx_t* idx, const void* payload, size_t n_bytes, hipMemcpyKind kind, uint32_t n_reads, std::vector<int64_t>&& off, const char* what)
 {
     if (hipSetDevice(idx->device) != hipSuccess) return 0;
     bwamem_batch_s* b = new bwamem_batch_s();
-    b->idx = idx; b->n_reads = n_reads;
+    b->idx = idx; b->n_reads = n_reads; b->n_bytes = n_bytes;
     b->h_off = std::move(off);
-    b->n_bytes = (size_t)b->h_off[n_reads];
-    bool ok = b->d_raw.ensure(b->n_bytes + 64) && b->d_seq.ensure(b->n_bytes + 64) && b->d_off.ensure(((size_t)n_reads + 1) * 8);
-    ok = ok && hipMemcpy(b->d_raw.p, payload, b->n_bytes, hipMemcpyHostToDevice) == hipSuccess
-            && hipMemcpy(b->d_off.p, b->h_off.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { fprintf(stderr, "[bwamem_hip] request upload failed\n"); bwamem_hip_batch_free(b); return 0; }
+    const bool ok = b->h_off[n_reads] == (int64_t)n_bytes
+        && b->d_raw.ensure(n_bytes + 64) && b->d_seq.ensure(n_bytes + 64) && b->d_off.ensure(((size_t)n_reads + 1) * 8)
+        && hipMemcpy(b->d_raw.p, payload, n_bytes, kind) == hipSuccess
+        && hipMemcpy(b->d_off.p, b->h_off.data(), ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) { fprintf(stderr, "[bwamem_hip] %s failed\n", what); bwamem_hip_batch_free(b); return 0; }
     return b;
 }
 
@@ -1656,7 +1644,7 @@ bwamem_batch_t* bwamem_hip_batch_upload(bwaidx_t* idx, const char* pSeq, size_t 
             p = z + 1;
         }
         off[n_reads] = p - (pSeq + 4);
-        return batch_from_offsets(idx, pSeq + 4, n_reads, std::move(off));
+        return resident_batch(idx, pSeq + 4, (size_t)off[n_reads], hipMemcpyHostToDevice, n_reads, std::move(off), "request upload");
     });
 }
 
@@ -1664,16 +1652,7 @@ bwamem_batch_t* bwamem_hip_batch_wrap_device(bwaidx_t* idx, const void* d_payloa
 {
     return guarded("bwamem_hip_batch_wrap_device", (bwamem_batch_t*)0, [&]() -> bwamem_batch_t* {
         if (!idx || !d_payload || !h_offsets) return 0;
-        if (hipSetDevice(idx->device) != hipSuccess) return 0;
-        bwamem_batch_s* b = new bwamem_batch_s();
-        b->idx = idx; b->n_reads = nReads; b->n_bytes = nBytes;
-        b->h_off.assign(h_offsets, h_offsets + (size_t)nReads + 1);
-        bool ok = b->h_off[nReads] == (int64_t)nBytes
-            && b->d_raw.ensure(nBytes + 64) && b->d_seq.ensure(nBytes + 64) && b->d_off.ensure(((size_t)nReads + 1) * 8)
-            && hipMemcpy(b->d_raw.p, d_payload, nBytes, hipMemcpyDeviceToDevice) == hipSuccess
-            && hipMemcpy(b->d_off.p, b->h_off.data(), ((size_t)nReads + 1) * 8, hipMemcpyHostToDevice) == hipSuccess;
-        if (!ok) { fprintf(stderr, "[bwamem_hip] batch_wrap_device failed\n"); bwamem_hip_batch_free(b); return 0; }
-        return b;
+        return resident_batch(idx, d_payload, nBytes, hipMemcpyDeviceToDevice, nReads, std::vector<int64_t>(h_offsets, h_offsets + (size_t)nReads + 1), "batch_wrap_device");
     });
 }
 
@@ -1750,8 +1729,6 @@ void bwamem_hip_batch_free(bwamem_batch_t* b)
     if (!b) return;
     (void)hipSetDevice(b->idx->device);
     release_tile_outputs(b);
-    pe_call_free(b);
-    b->d_raw.release(); b->d_seq.release(); b->d_off.release(); b->sink.pool.release();
     delete b;
 }
 
@@ -1777,7 +1754,12 @@ static void* create_alignments_split(bwaidx_s* ix0, const MemOpt& o, const MemPe
     const bool pe = (o.flag & MEM_F_PE) != 0, two_step = pe && !pes0;
     int D = (int)reps.size();
     if ((uint64_t)D > (uint64_t)n / (pe ? 2 : 1)) D = std::max<int>(1, (int)(n / (pe ? 2 : 1)));
-    struct Shard { const char* p = nullptr; uint32_t n = 0; int64_t id0 = 0; bool ready = false, p1_done = false, ok = false; bwamem_batch_s* b = nullptr; void* res = nullptr; size_t bytes = 0; };
+    struct Shard {
+        const char* p = nullptr; uint32_t n = 0; int64_t id0 = 0; bool ready = false, p1_done = false, ok = false; bwamem_batch_s* b = nullptr; void* res = nullptr; size_t bytes = 0;
+        Shard() = default;
+        Shard(const Shard&) = delete; Shard& operator=(const Shard&) = delete;
+        ~Shard() { free(res); if (b) bwamem_hip_batch_free(b); }
+    };
     std::vector<Shard> sh((size_t)D);
     uint32_t share = n / (uint32_t)D;
     if (pe) share &= ~1u;
@@ -1799,7 +1781,7 @@ static void* create_alignments_split(bwaidx_s* ix0, const MemOpt& o, const MemPe
                 cv.notify_all();
                 { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return stats_ready || failed; }); ok = ok && !failed; }
                 if (ok) ok = hipSetDevice(ix->device) == hipSuccess && pe_finish(ix, o, pes, sh[k].b);
-                else pe_call_free(sh[k].b);
+                else sh[k].b->pe.reset();
             }
             if (ok) { sh[k].bytes = sh[k].b->result_bytes; sh[k].res = sh[k].b->sink.take(sh[k].bytes); ok = sh[k].res != nullptr; }
         } catch (const std::exception& ex) { fprintf(stderr, "[bwamem_hip] createAlignments shard %d: %s\n", k, ex.what()); ok = false; }
@@ -1807,42 +1789,41 @@ static void* create_alignments_split(bwaidx_s* ix0, const MemOpt& o, const MemPe
         { std::lock_guard<std::mutex> lk(mu); sh[k].ok = ok; sh[k].p1_done = true; if (!ok) failed = true; }
         cv.notify_all();
     };
-    std::vector<std::thread> th;
-    for (int k = 0; k < D; ++k) th.emplace_back(run, k);
-    {   // the walk: shard k starts where the reads before it end
-        const char* p = payload;
+    {   // A throw on this thread (a shard thread that cannot start, candidates that cannot be gathered) fails the call: the
+        // shards are woken and joined here, freed with sh, and the exception reaches the export, which returns NULL.
+        ThreadGroup th([&] { { std::lock_guard<std::mutex> lk(mu); failed = true; stats_ready = true; } cv.notify_all(); });
+        for (int k = 0; k < D; ++k) th.spawn(run, k);
+        const char* p = payload;                    // the walk: shard k starts where the reads before it end
         for (int k = 0; k < D; ++k) {
             { std::lock_guard<std::mutex> lk(mu); sh[k].p = p; sh[k].ready = true; }
             cv.notify_all();
             if (k + 1 < D) { uint64_t got = 0; p = scan_reads(p, sh[k].n, (size_t)-1, &got); }
         }
-    }
-    if (two_step) {
-        { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { for (const Shard& s : sh) if (!s.p1_done) return false; return true; }); }
-        bool ok; { std::lock_guard<std::mutex> lk(mu); ok = !failed; }
-        if (ok) {
-            std::vector<int8_t> dir, d1; std::vector<int64_t> is, i1;
-            for (const Shard& s : sh) { pe_candidates(s.b, d1, i1); dir.insert(dir.end(), d1.begin(), d1.end()); is.insert(is.end(), i1.begin(), i1.end()); }
-            host_pestat(o, dir, is, pes);
+        if (two_step) {
+            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { for (const Shard& s : sh) if (!s.p1_done) return false; return true; }); }
+            bool ok; { std::lock_guard<std::mutex> lk(mu); ok = !failed; }
+            if (ok) {
+                std::vector<int8_t> dir, d1; std::vector<int64_t> is, i1;
+                for (const Shard& s : sh) { pe_candidates(s.b, d1, i1); dir.insert(dir.end(), d1.begin(), d1.end()); is.insert(is.end(), i1.begin(), i1.end()); }
+                host_pestat(o, dir, is, pes);
+            }
+            { std::lock_guard<std::mutex> lk(mu); stats_ready = true; }
+            cv.notify_all();
         }
-        { std::lock_guard<std::mutex> lk(mu); stats_ready = true; }
-        cv.notify_all();
+        th.join();
     }
-    for (std::thread& t : th) t.join();
-    void* res = nullptr;
+    if (failed) return nullptr;
     size_t total = 0;
-    if (!failed) {
-        for (const Shard& s : sh) total += s.bytes;
-        res = malloc(total ? total : 1);
-        if (res) {
-            std::vector<std::thread> cp;
-            size_t off = 0;
-            for (const Shard& s : sh) { uint8_t* dst = (uint8_t*)res + off; cp.emplace_back([dst, &s] { if (s.bytes) memcpy(dst, s.res, s.bytes); }); off += s.bytes; }
-            for (std::thread& t : cp) t.join();
-        }
-    }
-    for (Shard& s : sh) { if (s.res) free(s.res); if (s.b) bwamem_hip_batch_free(s.b); }
-    if (res && out_bytes) *out_bytes = total;
+    for (const Shard& s : sh) total += s.bytes;
+    uint8_t* res = (uint8_t*)malloc(total ? total : 1);
+    if (!res) return nullptr;
+    try {
+        ThreadGroup cp;
+        size_t off = 0;
+        for (const Shard& s : sh) { uint8_t* dst = res + off; cp.spawn([dst, &s] { if (s.bytes) memcpy(dst, s.res, s.bytes); }); off += s.bytes; }
+        cp.join();
+    } catch (...) { free(res); throw; }
+    if (out_bytes) *out_bytes = total;
     return res;
 }
 
@@ -1857,9 +1838,8 @@ void* jnibwa_createAlignments(bwaidx_t* pIdx, mem_opt_t* pOpts, mem_pestat_t* pe
     // With several replicas behind the handle (jnibwa_openIndex): a large call is cut across all of them; a small one goes to
     // the next replica in turn (the first free one from there), so that concurrent callers of one BwaMemIndex
     // (BwaMemIndex.java:16-27) spread over the devices instead of queueing on one.
-    void* res = 0;
     RoctxRange rr("jnibwa_createAlignments");
-    try {
+    return guarded("jnibwa_createAlignments", (void*)0, [&]() -> void* {
         uint32_t n; memcpy(&n, pSeq, 4);
         MemOpt o; memcpy(&o, pOpts, sizeof o);
         const int D = 1 + (int)pIdx->peers.size();
@@ -1867,7 +1847,7 @@ void* jnibwa_createAlignments(bwaidx_t* pIdx, mem_opt_t* pOpts, mem_pestat_t* pe
             static const long split_min = []{ const char* e = getenv("BWAMEM_HIP_SPLIT_MIN"); return e && atol(e) > 0 ? atol(e) : 131072L; }();   // reads per replica below which cutting a call does not pay
             if ((long)n >= split_min * D && n >= 2u * (unsigned)D) {
                 size_t bytes = 0;
-                res = create_alignments_split(pIdx, o, (const MemPestat*)peStats, pSeq + 4, n, &bytes);
+                void* res = create_alignments_split(pIdx, o, (const MemPestat*)peStats, pSeq + 4, n, &bytes);
                 if (res && pBufSize) *pBufSize = bytes;
                 return res;
             }
@@ -1883,16 +1863,15 @@ void* jnibwa_createAlignments(bwaidx_t* pIdx, mem_opt_t* pOpts, mem_pestat_t* pe
             }
             if (!lk.owns_lock()) { ix = first % D == 0 ? pIdx : pIdx->peers[first % D - 1]; lk = std::unique_lock<std::mutex>(ix->mu); }
         } else lk = std::unique_lock<std::mutex>(ix->mu);
-        bwamem_batch_s* b = new_streamed_batch(ix, pSeq + 4, n);
-        if (align_batch(ix, o, (const MemPestat*)peStats, b, 0)) {
+        std::unique_ptr<bwamem_batch_s, void (*)(bwamem_batch_t*)> b(new_streamed_batch(ix, pSeq + 4, n), bwamem_hip_batch_free);
+        void* res = 0;
+        if (align_batch(ix, o, (const MemPestat*)peStats, b.get(), 0)) {
             res = b->sink.take(b->result_bytes);
             if (res && pBufSize) *pBufSize = b->result_bytes;
         }
-        lk.unlock();
-        bwamem_hip_batch_free(b);
-    } catch (const std::exception& ex) { fprintf(stderr, "[bwamem_hip] createAlignments: %s\n", ex.what()); res = 0; }
-      catch (...) { res = 0; }
-    return res;
+        lk.unlock();                                // (the batch is freed after the replica's lock is released)
+        return res;
+    });
 }
 
 } // extern "C"
