@@ -37,6 +37,8 @@ _lib.jnibwa_createAlignments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctype
 _lib.jnibwa_createDefaultOptions.restype = ctypes.c_void_p
 _lib.jnibwa_free.argtypes = [ctypes.c_void_p]
 _lib.jnibwa_getVersion.restype = ctypes.c_char_p
+_lib.bwamem_hip_align_to_bam.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int]
 
 
 class CouldNotReadImageException(RuntimeError):
@@ -319,6 +321,33 @@ class BwaMemAligner:
             return self.index.doAlignment(contigBuf, opts, self.pairEndStats)
         finally:
             self.index.deRefIndex()
+
+    def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s):
+        """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
+        `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
+        "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred)."""
+        opts = self._getOpts()
+        seqs = [func(e) for e in sequences]
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        if names is not None and len(names) != len(seqs):
+            raise ValueError("%d names for %d sequences" % (len(names), len(seqs)))
+        buf = struct.pack("=i", len(seqs)) + b"".join(s + b"\0" for s in seqs)
+        arr = None
+        if names is not None:
+            arr = (ctypes.c_char_p * len(names))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
+        pes = self.pairEndStats
+        pb = ctypes.create_string_buffer(pes._pack(), 128) if pes is not None else None
+        self.index.refIndex()
+        try:
+            fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+            try:
+                rc = _lib.bwamem_hip_align_to_bam(self.index.indexAddress, opts, pb, buf, len(buf), arr, level, fd, 1)
+            finally:
+                os.close(fd)
+        finally:
+            self.index.deRefIndex()
+        if rc != 0:
+            raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s" % (self.index.indexImageFile, path))
 
     def alignSeqs(self, sequences, func=lambda s: s):
         """BwaMemAligner.java:192-310: one list of BwaMemAlignment per input sequence"""

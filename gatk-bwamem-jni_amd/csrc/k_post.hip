@@ -124,6 +124,88 @@ __global__ void k_pack(TileView tv, uint8_t* dst)
     for (int i = sub; i < nw; i += 8) d[i] = src[i];
 }
 
+// ------------------------------------------------------------------ BAM records from the packed response (bam_encode.h)
+// Three steps like k_final_se / launch_scan / k_pack: the bytes of every read's records, a scan, and the records themselves.
+// step 1: one lane per read walks the read's response records and adds up the sizes of their BAM records
+__global__ void __launch_bounds__(64) k_bam_size(BamTile t)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= t.n_reads) return;
+    const int64_t lo = t.resp_off[r], hi = t.resp_off[r + 1];
+    int64_t total = 0;
+    int err = 0;
+    if (hi > lo) {                                                   // (an odd trailing read of a paired call has no bytes: no record)
+        const uint32_t* p = (const uint32_t*)(t.resp + lo);
+        const int64_t n = (hi - lo) >> 2;
+        const int32_t l_read = (int32_t)(t.raw_off[r + 1] - t.raw_off[r] - 1);
+        const int32_t n_aln = (int32_t)p[0];
+        int64_t at = 1;
+        if (n_aln < 0 || l_read < 0 || ((hi - lo) & 3)) err = BAM_ERR_PARSE;
+        for (int32_t k = 0; k < n_aln && !err; ++k) {
+            BamRec R;
+            err = bam_parse(p + at, n - at, k, l_read, t.n_seqs, R);
+            if (err) break;
+            bam_name(t, r, R);
+            if (bam_layout(R) < 0) { err = BAM_ERR_SPAN; break; }
+            total += R.total; at += R.words;
+        }
+        if (!err && at != n) err = BAM_ERR_PARSE;
+        if (!err && total > 0x7fffffff) err = BAM_ERR_SPAN;
+    }
+    t.sizes[r] = err ? 0 : (int32_t)total;
+    if (err) atomicOr(t.err, err);
+}
+
+// step 3: G lanes per read (8, or the wavefront for tiles of long reads) write the read's records.  Every lane parses the record
+// (the same few words for all of them); the lanes then share out the aligned 32-bit words of the record's span in the output,
+// each assembled in a register from bam_byte and stored whole.  Only the up to three bytes before the first aligned word
+// and after the last are stored singly.
+template <int G>
+__global__ void __launch_bounds__(256) k_bam_emit(BamTile t)
+{
+    const int r = blockIdx.x * (256 / G) + ((int)threadIdx.x / G), sub = (int)threadIdx.x % G;
+    if (r >= t.n_reads) return;
+    const int64_t lo = t.resp_off[r], hi = t.resp_off[r + 1];
+    int64_t o = t.out_off[r];
+    const int64_t o_end = t.out_off[r + 1];
+    if (hi <= lo || o_end <= o) return;                              // no record (or refused by the size kernel, which flagged it)
+    const uint32_t* p = (const uint32_t*)(t.resp + lo);
+    const int64_t n = (hi - lo) >> 2;
+    const uint8_t* raw = t.raw + t.raw_off[r];
+    const int32_t l_read = (int32_t)(t.raw_off[r + 1] - t.raw_off[r] - 1);
+    const int32_t n_aln = (int32_t)p[0];
+    int64_t at = 1;
+    for (int32_t k = 0; k < n_aln; ++k) {
+        BamRec R;
+        int err = bam_parse(p + at, n - at, k, l_read, t.n_seqs, R);
+        if (!err) { bam_name(t, r, R); if (bam_layout(R) < 0 || o + R.total > o_end) err = BAM_ERR_SPAN; }    // never outside the read's span
+        if (err) { if (sub == 0) atomicOr(t.err, err); return; }
+        uint8_t* dst = t.out + o;
+        const int32_t lead = (int32_t)((4 - (o & 3)) & 3), head = R.total < lead ? R.total : lead;
+        const int32_t nw = (R.total - head) >> 2, tail = R.total - head - 4 * nw;
+        if (sub < head) dst[sub] = bam_byte(R, raw, sub);
+        uint32_t* dw = (uint32_t*)(dst + head);
+        for (int32_t w = sub; w < nw; w += G) {
+            const int32_t i = head + 4 * w;
+            dw[w] = (uint32_t)bam_byte(R, raw, i) | (uint32_t)bam_byte(R, raw, i + 1) << 8 | (uint32_t)bam_byte(R, raw, i + 2) << 16 | (uint32_t)bam_byte(R, raw, i + 3) << 24;
+        }
+        if (sub < tail) dst[head + 4 * nw + sub] = bam_byte(R, raw, head + 4 * nw + sub);
+        o += R.total; at += R.words;
+    }
+}
+
+void launch_bam_size(hipStream_t st, const BamTile& t)
+{
+    if (t.n_reads <= 0) return;
+    hipLaunchKernelGGL(k_bam_size, dim3((t.n_reads + 63) / 64), dim3(64), 0, st, t);
+}
+void launch_bam_emit(hipStream_t st, const BamTile& t)
+{
+    if (t.n_reads <= 0) return;
+    if (t.max_len > 1000) hipLaunchKernelGGL(k_bam_emit<64>, dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);      // long reads: a wavefront per read
+    else hipLaunchKernelGGL(k_bam_emit<8>, dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
+}
+
 void launch_post1(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv)
 {
     if (tv.n_reads <= 0) return;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bwamem_types.h"
+#include "bam_encode.h"
 
 void launch_build_occ64(hipStream_t st, const uint32_t* bwt, uint64_t n_blocks, uint4* occ);
 // suffix array at every ix.sa_intv-th rank (lo/hi, (seq_len >> sa_shift) + 1 entries) from the image's sampling; *err: device int, OR-ed on failure
@@ -29,6 +30,9 @@ void launch_gcigar(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const 
                    uint8_t* zpool, unsigned long long zpool_cap, unsigned long long* zpool_cur, uint8_t* slabs, size_t slab_bytes, int* queue);
 void launch_final_se(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv, const void* job_out, const uint32_t* job_cig, int cig_cap);
 void launch_pack(hipStream_t st, const TileView& tv, uint8_t* dst);
+// BAM records of a tile's packed response (bam_encode.h): sizes per read, then -- after a launch_scan over the batch -- the records
+void launch_bam_size(hipStream_t st, const BamTile& t);
+void launch_bam_emit(hipStream_t st, const BamTile& t);
 
 // paired-end path (k_pe.hip)
 void launch_pestat_cand(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv, int8_t* cand_dir, int64_t* cand_is);

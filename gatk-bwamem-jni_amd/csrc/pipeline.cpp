@@ -264,7 +264,11 @@ struct bwaidx_s {
     ~bwaidx_s() { if (up_stream) (void)hipStreamDestroy(up_stream); }
 };
 
-struct TileOut { uint8_t* d = nullptr; size_t bytes = 0; bool owned = false; };
+struct TileOut {
+    uint8_t* d = nullptr; size_t bytes = 0; bool owned = false;
+    // kept only when the caller asked for it (bwamem_hip_batch_keep_offsets): the reads' offsets within d, [n_reads + 1] (owned), for the BAM encoder
+    int64_t* d_off = nullptr; int64_t read_id = 0; int n_reads = 0, max_len = 0;
+};
 
 // A tile of a paired-end call between its two phases (regions per read, in HBM), and what phase 1 of a call leaves behind
 // for phase 2.  (A single-pass call frees each tile's regions as soon as its phase 2 is done: pe_begin.)
@@ -351,6 +355,11 @@ struct bwamem_batch_s {
     OutSink sink;
     size_t result_bytes = 0;
     std::unique_ptr<PeCall> pe;     // paired-end call split in two steps (bwamem_hip_batch_pe_begin / _finish): phase-1 products kept in HBM
+    // BAM records of the resident results (bwamem_hip_batch_encode_bam)
+    bool keep_offsets = false, aligned = false;      // aligned: the tiles hold the results of a finished call
+    int64_t read_id0 = 0;                            // of that call
+    DevBuf bam, bam_sizes, bam_off, bam_scan_tmp, bam_names, bam_name_off, bam_err;
+    size_t bam_bytes = 0;
 };
 
 static const int LOG_TAB_N = 1 << 20;
@@ -779,6 +788,11 @@ static bool emit_tile(Workspace& ws, bwamem_batch_s* b, size_t tile_index, const
         if (dst) to.d = dst;
         else { HIP_OK(hipMalloc((void**)&to.d, (size_t)out_total)); to.owned = true; }
         TIMED(ws, K_PACK, launch_pack(ws.stream, tv, to.d));
+        if (b->keep_offsets) {
+            HIP_OK(hipMalloc((void**)&to.d_off, ((size_t)tv.n_reads + 1) * 8));
+            HIP_OK(hipMemcpyAsync(to.d_off, tv.out_off, ((size_t)tv.n_reads + 1) * 8, hipMemcpyDeviceToDevice, ws.stream));
+            to.read_id = tv.read_id0; to.n_reads = tv.n_reads; to.max_len = tv.max_len;
+        }
         HIP_OK(hipStreamSynchronize(ws.stream));
     }
     return true;
@@ -1324,7 +1338,7 @@ static bool pe_finish(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes, bwa
         }
         return true;
     }, [&] { failed = true; b->sink.abort(); });
-    if (!failed) { for (const TileOut& t : b->tiles) b->result_bytes += t.bytes; b->sink.last_total = b->result_bytes; }
+    if (!failed) { for (const TileOut& t : b->tiles) b->result_bytes += t.bytes; b->sink.last_total = b->result_bytes; b->aligned = true; }
     b->pe.reset();
     return !failed;
 }
@@ -1353,8 +1367,8 @@ static bool align_batch_pe(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes
 
 static void release_tile_outputs(bwamem_batch_s* b)
 {
-    for (TileOut& t : b->tiles) if (t.d && t.owned) (void)hipFree(t.d);
-    b->tiles.clear(); b->result_bytes = 0;
+    for (TileOut& t : b->tiles) { if (t.d && t.owned) (void)hipFree(t.d); if (t.d_off) (void)hipFree(t.d_off); }
+    b->tiles.clear(); b->result_bytes = 0; b->aligned = false; b->bam_bytes = 0;
 }
 
 // Tiles are independent, and every kernel of a tile ends in a tail of a few long-running reads; several tiles are
@@ -1370,7 +1384,8 @@ static bool align_batch(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes, b
     release_tile_outputs(b);
     b->pe.reset();
     b->sink.begin_call(b->n_reads);
-    if (b->n_reads == 0) return true;
+    b->read_id0 = read_id0;
+    if (b->n_reads == 0) { b->aligned = pe_step != 1; return true; }
     if (!b->h_payload) {                                   // resident batch: fresh working copy of the bases
         HIP_OK(hipMemcpyAsync(b->d_seq.p, b->d_raw.p, b->n_bytes, hipMemcpyDeviceToDevice, ws.stream));
         TIMED(ws, K_ENCODE, launch_encode(ws.stream, b->d_seq.as<uint8_t>(), (int64_t)b->n_bytes));
@@ -1393,7 +1408,7 @@ static bool align_batch(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes, b
         });
         if (ok) for (const TileOut& t : b->tiles) b->result_bytes += t.bytes;
     }
-    if (ok && pe_step != 1) b->sink.last_total = b->result_bytes;
+    if (ok && pe_step != 1) { b->sink.last_total = b->result_bytes; b->aligned = true; }
     return ok;
 }
 
@@ -1720,6 +1735,94 @@ int bwamem_hip_batch_download(bwamem_batch_t* b, void* dst)
             if (t.bytes && hipMemcpy(p, t.d, t.bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
             p += t.bytes;
         }
+        return 0;
+    });
+}
+
+// ---- BAM records of the resident results (bam_encode.h; kernels next to k_pack)
+static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const int64_t* name_off)
+{
+    bwaidx_s* ix = b->idx;
+    HIP_OK(hipSetDevice(ix->device));
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    b->bam_bytes = 0;
+    if (!b->keep_offsets) { fprintf(stderr, "[bwamem_hip] encode_bam: the batch was aligned without bwamem_hip_batch_keep_offsets\n"); return false; }
+    if (!b->aligned) { fprintf(stderr, "[bwamem_hip] encode_bam: the batch holds no finished alignment\n"); return false; }
+    if ((names == nullptr) != (name_off == nullptr)) { fprintf(stderr, "[bwamem_hip] encode_bam: names and their offsets go together\n"); return false; }
+    const size_t n = b->n_reads;
+    if (n == 0) return true;
+    if (n >= 0x7fffffffu) { fprintf(stderr, "[bwamem_hip] encode_bam: too many reads\n"); return false; }
+    if (names) {
+        if (name_off[0] < 0) { fprintf(stderr, "[bwamem_hip] encode_bam: negative name offset\n"); return false; }
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t l = name_off[i + 1] - name_off[i];
+            if (l < 1 || l > 254) { fprintf(stderr, "[bwamem_hip] encode_bam: the name of read %zu has %lld bytes (1..254 allowed)\n", i, (long long)l); return false; }
+        }
+        if (!b->bam_names.ensure((size_t)name_off[n] + 8) || !b->bam_name_off.ensure((n + 1) * 8)) return false;
+        HIP_OK(hipMemcpyAsync(b->bam_names.p, names, (size_t)name_off[n], hipMemcpyHostToDevice, ws.stream));
+        HIP_OK(hipMemcpyAsync(b->bam_name_off.p, name_off, (n + 1) * 8, hipMemcpyHostToDevice, ws.stream));
+    }
+    if (!(b->bam_sizes.ensure(n * 4) && b->bam_off.ensure((n + 1) * 8) && b->bam_scan_tmp.ensure(scan_tmp_bytes((int64_t)n + 1)) && b->bam_err.ensure(64))) return false;
+    HIP_OK(hipMemsetAsync(b->bam_sizes.p, 0, n * 4, ws.stream));       // reads no tile covers have no record
+    HIP_OK(hipMemsetAsync(b->bam_err.p, 0, 64, ws.stream));
+    std::vector<BamTile> tiles;
+    for (const TileOut& to : b->tiles) {
+        if (!to.d_off || to.n_reads <= 0) continue;
+        const int64_t r0 = to.read_id - b->read_id0;
+        if (r0 < 0 || (uint64_t)r0 + (uint64_t)to.n_reads > n) { fprintf(stderr, "[bwamem_hip] encode_bam: internal error: tile outside the batch\n"); return false; }
+        BamTile t; memset(&t, 0, sizeof t);
+        t.resp = to.d; t.resp_off = to.d_off; t.n_reads = to.n_reads; t.max_len = to.max_len;
+        t.raw = b->d_raw.as<uint8_t>(); t.raw_off = b->d_off.as<int64_t>() + r0;
+        t.read_index0 = to.read_id; t.paired = paired != 0; t.n_seqs = ix->d.n_seqs;
+        if (names) { t.names = b->bam_names.as<uint8_t>(); t.name_off = b->bam_name_off.as<int64_t>() + r0; }
+        t.sizes = b->bam_sizes.as<int32_t>() + r0; t.out_off = b->bam_off.as<int64_t>() + r0; t.out = nullptr; t.err = b->bam_err.as<int32_t>();
+        tiles.push_back(t);
+    }
+    for (const BamTile& t : tiles) launch_bam_size(ws.stream, t);
+    launch_scan(ws.stream, b->bam_sizes.as<int32_t>(), b->bam_off.as<int64_t>(), (int)n, b->bam_scan_tmp.as<int64_t>());
+    HIP_OK(hipGetLastError());
+    int64_t total = 0; int32_t err = 0;
+    HIP_OK(hipMemcpyAsync(&total, b->bam_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(&err, b->bam_err.p, 4, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
+    if (err & BAM_ERR_CIGAR_OPS) { fprintf(stderr, "[bwamem_hip] encode_bam: a record has more than %d CIGAR operations (not representable without the CG tag)\n", BAM_MAX_CIGAR_OPS); return false; }
+    if (err || total < 0) { fprintf(stderr, "[bwamem_hip] encode_bam: the resident response does not parse (flags %d)\n", err); return false; }
+    if (total == 0) return true;
+    if (!b->bam.ensure((size_t)total)) return false;
+    for (BamTile& t : tiles) { t.out = b->bam.as<uint8_t>(); launch_bam_emit(ws.stream, t); }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(&err, b->bam_err.p, 4, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
+    if (err) { fprintf(stderr, "[bwamem_hip] encode_bam: internal error while writing the records (flags %d)\n", err); return false; }
+    b->bam_bytes = (size_t)total;
+    return true;
+}
+
+int bwamem_hip_batch_keep_offsets(bwamem_batch_t* b, int on)
+{
+    if (!b) return -1;
+    b->keep_offsets = on != 0;
+    return 0;
+}
+
+int bwamem_hip_batch_encode_bam(bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off)
+{
+    return guarded("bwamem_hip_batch_encode_bam", -1, [&]() -> int {
+        if (!b || !b->idx) return -1;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        return encode_bam(b, paired, names, name_off) ? 0 : -1;
+    });
+}
+
+size_t bwamem_hip_batch_bam_bytes(const bwamem_batch_t* b) { return b ? b->bam_bytes : 0; }
+
+int bwamem_hip_batch_bam_download(bwamem_batch_t* b, void* dst)
+{
+    return guarded("bwamem_hip_batch_bam_download", -1, [&]() -> int {
+        if (!b || (!dst && b->bam_bytes)) return -1;
+        if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+        if (b->bam_bytes && hipMemcpy(dst, b->bam.p, b->bam_bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
         return 0;
     });
 }

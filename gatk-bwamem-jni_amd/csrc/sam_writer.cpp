@@ -12,12 +12,28 @@
 //   * RNEXT/PNEXT/TLEN from the record's mate fields ("=" for the same contig); unmapped reads of a pair take their mate's place;
 //   * tags NM:i MD:Z AS:i XS:i and XA:Z when the record has them.
 // Read names: supplied by the caller, else "r<index>" (paired: "p<pair index>" for both mates).
+// Two deliberate deviations from upstream's text are kept: a secondary record carries its SEQ (upstream writes '*'), and records
+// on ALT contigs keep their soft clips as the rule above treats every later record (upstream keeps soft clips on ALT hits).
+//
+// The BAM encoder (bam_encode.h, kernels in k_post.hip) is bound to the same rules: a BAM record must decode to exactly the line
+// written here for the same response record, the two deviations included.  This file also holds the host side of the BAM
+// path: the uncompressed BAM header, BGZF framing by worker threads, and bwamem_hip_align_to_bam.
+// BGZF (SAM specification 4.1): blocks of at most 0xff00 input bytes, each a gzip member with the BC extra field, then the
+// 28-byte EOF block.  Level 0 writes stored deflate blocks with a CRC-32 of its own and needs nothing else; levels 1..9 take
+// compress2 and crc32 from libz.so.1, loaded at run time (a zlib stream minus its 2-byte header and 4-byte Adler-32 trailer is
+// the raw deflate stream a gzip member wants).  Without that library levels >= 1 fail and level 0 still works.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <errno.h>
+#include <unistd.h>
+#include <dlfcn.h>
+#include <atomic>
 #include <string>
+#include <thread>
 #include <vector>
+#include "bam_encode.h"
 #include "index_io.h"
 #include "../../include/bwamem_hip.h"
 
@@ -38,6 +54,126 @@ inline char comp(char c)
     switch (c) { case 'A': return 'T'; case 'C': return 'G'; case 'G': return 'C'; case 'T': return 'A';
                  case 'a': return 't'; case 'c': return 'g'; case 'g': return 'c'; case 't': return 'a'; default: return c; }
 }
+
+// ---- BGZF
+const size_t BGZF_BLOCK = 0xff00;                       // input bytes per block at most
+const size_t BGZF_OVERHEAD = 18 + 5 + 8;                // header, one stored-block header, CRC32 + ISIZE
+const uint8_t BGZF_EOF[28] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+
+struct Crc32 {                                          // slice-by-8, reflected polynomial 0xEDB88320
+    uint32_t t[8][256];
+    Crc32() {
+        for (uint32_t i = 0; i < 256; ++i) { uint32_t c = i; for (int k = 0; k < 8; ++k) c = c & 1 ? 0xEDB88320u ^ (c >> 1) : c >> 1; t[0][i] = c; }
+        for (uint32_t i = 0; i < 256; ++i) for (int k = 1; k < 8; ++k) t[k][i] = t[0][t[k - 1][i] & 0xff] ^ (t[k - 1][i] >> 8);
+    }
+    uint32_t of(const uint8_t* p, size_t n) const {
+        uint32_t c = 0xffffffffu;
+        while (n >= 8) {
+            uint32_t a, b; memcpy(&a, p, 4); memcpy(&b, p + 4, 4);
+            a ^= c;
+            c = t[7][a & 0xff] ^ t[6][a >> 8 & 0xff] ^ t[5][a >> 16 & 0xff] ^ t[4][a >> 24] ^ t[3][b & 0xff] ^ t[2][b >> 8 & 0xff] ^ t[1][b >> 16 & 0xff] ^ t[0][b >> 24];
+            p += 8; n -= 8;
+        }
+        while (n--) c = t[0][(c ^ *p++) & 0xff] ^ (c >> 8);
+        return ~c;
+    }
+};
+const Crc32& crc_tab() { static const Crc32 c; return c; }
+
+struct Zlib {                                           // compress2 and crc32 of libz.so.1, if it is there
+    typedef int (*compress2_t)(unsigned char*, unsigned long*, const unsigned char*, unsigned long, int);
+    typedef unsigned long (*crc32_t)(unsigned long, const unsigned char*, unsigned int);
+    compress2_t compress2 = nullptr; crc32_t crc32 = nullptr;
+    Zlib() {
+        void* h = dlopen("libz.so.1", RTLD_NOW | RTLD_LOCAL);
+        if (!h) return;
+        compress2 = (compress2_t)dlsym(h, "compress2"); crc32 = (crc32_t)dlsym(h, "crc32");
+        if (!compress2 || !crc32) compress2 = nullptr, crc32 = nullptr;
+    }
+};
+const Zlib& zlib() { static const Zlib z; return z; }
+
+inline void le16(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
+inline void le32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+
+// one BGZF block of n <= BGZF_BLOCK input bytes into dst (room for n + BGZF_OVERHEAD) -> its size
+size_t bgzf_block(const uint8_t* src, size_t n, int level, uint8_t* dst)
+{
+    static const uint8_t head[16] = { 0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0 };
+    memcpy(dst, head, 16);
+    uint8_t* c = dst + 18;
+    size_t n_c = 0;
+    if (level > 0) {
+        // the zlib stream lands two bytes early, so that its deflate data starts at c; the two bytes it overwrites are rewritten below
+        unsigned long len = (unsigned long)(n + BGZF_OVERHEAD - 16);
+        if (zlib().compress2(dst + 16, &len, src, (unsigned long)n, level) == 0 && len >= 6 && len - 6 <= n + 5) n_c = (size_t)len - 6;
+    }
+    if (n_c == 0) {                                     // level 0 (or deflate made it longer): one stored block
+        c[0] = 1; le16(c + 1, (uint32_t)n); le16(c + 3, ~(uint32_t)n & 0xffff);
+        if (n) memcpy(c + 5, src, n);
+        n_c = n + 5;
+    }
+    const size_t total = 18 + n_c + 8;
+    le16(dst + 16, (uint32_t)(total - 1));
+    const uint32_t crc = level > 0 ? (uint32_t)zlib().crc32(zlib().crc32(0, nullptr, 0), src, (unsigned int)n) : crc_tab().of(src, n);
+    le32(c + n_c, crc); le32(c + n_c + 4, (uint32_t)n);
+    return total;
+}
+
+int bgzf_threads(int n_threads, size_t n_blocks)
+{
+    int cap = 16;                                       // not the machine's core count: the process shares the host with others
+    { const char* e = getenv("BWAMEM_HIP_BGZF_MAX_THREADS"); if (e && atoi(e) > 0) cap = atoi(e); }
+    if (n_threads <= 0 || n_threads > cap) n_threads = cap;
+    if ((size_t)n_threads > n_blocks) n_threads = (int)n_blocks;
+    return n_threads < 1 ? 1 : n_threads;
+}
+
+// src as BGZF blocks (+ the EOF block): malloc'ed, or null
+uint8_t* bgzf_compress(const uint8_t* src, size_t n, int level, int n_threads, bool with_eof, size_t* out_bytes)
+{
+    *out_bytes = 0;
+    if (level < 0 || level > 9 || (n && !src)) return nullptr;
+    if (level > 0 && !zlib().compress2) { fprintf(stderr, "[bwamem_hip] bgzf: libz.so.1 could not be loaded; only level 0 is available\n"); return nullptr; }
+    const size_t n_blocks = (n + BGZF_BLOCK - 1) / BGZF_BLOCK, slot = BGZF_BLOCK + BGZF_OVERHEAD;
+    uint8_t* out = (uint8_t*)malloc(n_blocks * slot + sizeof BGZF_EOF);
+    if (!out) return nullptr;
+    std::vector<uint32_t> size(n_blocks);
+    std::atomic<size_t> next(0);
+    auto work = [&]() {
+        for (;;) {
+            const size_t i = next++;
+            if (i >= n_blocks) return;
+            const size_t at = i * BGZF_BLOCK, len = n - at < BGZF_BLOCK ? n - at : BGZF_BLOCK;
+            size[i] = (uint32_t)bgzf_block(src + at, len, level, out + i * slot);
+        }
+    };
+    {
+        std::vector<std::thread> th;
+        const int nt = bgzf_threads(n_threads, n_blocks);
+        try { for (int k = 1; k < nt; ++k) th.emplace_back(work); } catch (...) { /* fewer threads: the others take the blocks */ }
+        work();
+        for (std::thread& t : th) t.join();
+    }
+    size_t o = 0;
+    for (size_t i = 0; i < n_blocks; ++i) { if (o != i * slot) memmove(out + o, out + i * slot, size[i]); o += size[i]; }
+    if (with_eof) { memcpy(out + o, BGZF_EOF, sizeof BGZF_EOF); o += sizeof BGZF_EOF; }
+    *out_bytes = o;
+    return out;
+}
+
+bool write_all(int fd, const uint8_t* p, size_t n)
+{
+    while (n) {
+        const ssize_t w = write(fd, p, n);
+        if (w < 0) { if (errno == EINTR) continue; return false; }
+        p += w; n -= (size_t)w;
+    }
+    return true;
+}
+
+struct Freed { void* p; explicit Freed(void* p_ = nullptr) : p(p_) {} ~Freed() { free(p); } Freed(const Freed&) = delete; Freed& operator=(const Freed&) = delete; };
+struct BatchOwner { bwamem_batch_t* b; ~BatchOwner() { bwamem_hip_batch_free(b); } };
 
 }  // namespace
 
@@ -155,6 +291,90 @@ char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* re
         if (pBytes) *pBytes = o.s.size();
         return res;
     } catch (...) { return 0; }
+}
+
+// ---- BAM
+void* bwamem_hip_bam_header(bwaidx_t* idx, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    if (!idx) return 0;
+    try {
+        size_t l_text = 0;
+        Freed text(bwamem_hip_sam_header(idx, &l_text));
+        if (!text.p || l_text > 0x7fffffff) return 0;
+        const std::vector<ContigInfo>& contigs = bwamem_index_contigs(idx);
+        std::string o("BAM\1", 4);
+        auto put32 = [&](int32_t v) { uint8_t b[4]; le32(b, (uint32_t)v); o.append((const char*)b, 4); };
+        put32((int32_t)l_text); o.append((const char*)text.p, l_text);
+        put32((int32_t)contigs.size());
+        for (const ContigInfo& c : contigs) {
+            if (c.len > 0x7fffffff) return 0;
+            put32((int32_t)c.name.size() + 1); o.append(c.name.c_str(), c.name.size() + 1); put32((int32_t)c.len);
+        }
+        void* r = malloc(o.size() ? o.size() : 1);
+        if (!r) return 0;
+        memcpy(r, o.data(), o.size());
+        if (pBytes) *pBytes = o.size();
+        return r;
+    } catch (...) { return 0; }
+}
+
+void* bwamem_hip_bgzf_compress(const void* src, size_t n, int level, int n_threads, int with_eof, size_t* pBytes)
+{
+    size_t bytes = 0;
+    void* r = 0;
+    try { r = bgzf_compress((const uint8_t*)src, n, level, n_threads, with_eof != 0, &bytes); } catch (...) { r = 0; }
+    if (pBytes) *pBytes = r ? bytes : 0;
+    return r;
+}
+
+int64_t bwamem_hip_bam_record_bytes(const void* rec, size_t n_words, int k, int32_t l_read, int32_t l_name)
+{
+    try {
+        if (!rec || l_read < 0 || l_name < 1 || l_name > 254) return -BAM_ERR_PARSE;
+        BamRec R;
+        const int err = bam_parse((const uint32_t*)rec, (int64_t)n_words, k, l_read, 0x7fffffff, R);
+        if (err) return -err;
+        R.name = 0; R.name_letter = 0; R.name_idx = 0; R.l_name = l_name;
+        const int32_t t = bam_layout(R);
+        return t < 0 ? -BAM_ERR_SPAN : t;
+    } catch (...) { return -BAM_ERR_PARSE; }
+}
+
+int bwamem_hip_align_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
+                            int level, int fd, int write_header)
+{
+    try {
+        if (!idx || !opt || !pSeq || nBytes < 4 || fd < 0 || level < 0 || level > 9) return -1;
+        if (level > 0 && !zlib().compress2) { fprintf(stderr, "[bwamem_hip] align_to_bam: libz.so.1 could not be loaded; only level 0 is available\n"); return -1; }
+        uint32_t n_reads; memcpy(&n_reads, pSeq, 4);
+        int32_t flag; memcpy(&flag, (const char*)opt + 60, 4);                  // mem_opt_t.flag (BwaMemAligner.java:75)
+        const int paired = (flag & 0x2) != 0;
+        std::string blob; std::vector<int64_t> name_off;
+        if (readNames) {
+            name_off.reserve((size_t)n_reads + 1);
+            for (uint32_t i = 0; i < n_reads; ++i) { name_off.push_back((int64_t)blob.size()); if (readNames[i]) blob += readNames[i]; }
+            name_off.push_back((int64_t)blob.size());
+        }
+        BatchOwner bo{ bwamem_hip_batch_upload(idx, pSeq, nBytes) };
+        if (!bo.b) return -1;
+        if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
+        if (bwamem_hip_batch_encode_bam(bo.b, paired, readNames ? blob.data() : nullptr, readNames ? name_off.data() : nullptr) != 0) return -1;
+        const size_t n = bwamem_hip_batch_bam_bytes(bo.b);
+        Freed recs(malloc(n ? n : 1));
+        if (!recs.p || bwamem_hip_batch_bam_download(bo.b, recs.p) != 0) return -1;
+        if (write_header) {
+            size_t nh = 0, nz = 0;
+            Freed hdr(bwamem_hip_bam_header(idx, &nh));
+            if (!hdr.p) return -1;
+            Freed z(bgzf_compress((const uint8_t*)hdr.p, nh, level, 0, false, &nz));
+            if (!z.p || !write_all(fd, (const uint8_t*)z.p, nz)) return -1;
+        }
+        size_t nz = 0;
+        Freed z(bgzf_compress((const uint8_t*)recs.p, n, level, 0, true, &nz));
+        if (!z.p || !write_all(fd, (const uint8_t*)z.p, nz)) return -1;
+        return 0;
+    } catch (...) { return -1; }
 }
 
 }  // extern "C"

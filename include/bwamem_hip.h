@@ -109,6 +109,38 @@ void bwamem_hip_batch_free(bwamem_batch_t* b);
 char* bwamem_hip_sam_header(bwaidx_t* idx, size_t* pBytes);
 char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired, size_t* pBytes);
 
+/* BAM on the native side (additive).  The records are encoded on the device, straight from the results
+ * resident after bwamem_hip_batch_align / _pe_finish; the host only frames BGZF.  A BAM record decodes to exactly the SAM
+ * line bwamem_hip_response_to_sam writes for the same response record (rules: csrc/bam_encode.h).
+ *   _keep_offsets   before _align / _pe_begin: keep each tile's per-read offsets (8 bytes per read) for the encoder.  Off by
+ *                   default, and then the align path allocates and computes exactly what it did without this block.
+ *   _encode_bam     uncompressed BAM alignment records (block_size-prefixed, SAM spec 4.2) in response order, into a device
+ *                   buffer owned by the batch.  paired = the call carried MEM_F_PE.  names = all names back to back (host
+ *                   memory), name_off = nReads + 1 offsets into it, each name 1..254 bytes; or both NULL: "r<index>",
+ *                   paired "p<pair index>", the index counted from read_id0 of the align call.  An odd trailing read of a
+ *                   paired call has no record.  Non-zero on error: no offsets kept, no finished alignment, a bad name, or a
+ *                   record with more than 65 535 CIGAR operations (the CG-tag convention is not implemented); nothing is
+ *                   produced then.
+ *   _bam_bytes / _bam_download   size of those records, and their copy to host memory
+ *   bwamem_hip_bam_header        the uncompressed BAM header: magic, the text of bwamem_hip_sam_header, the contig table
+ *   bwamem_hip_bgzf_compress     BGZF blocks (at most 0xff00 input bytes each) by n_threads workers (<= 0 or more than 16:
+ *                   16), with_eof: followed by the 28-byte EOF block.  level 0 = stored blocks, always available; levels
+ *                   1..9 need libz.so.1 at run time (NULL without it).  The result does not depend on n_threads.
+ *   bwamem_hip_align_to_bam      upload, align, encode, download, BGZF, write(fd): the header first when write_header is set, the
+ *                   EOF block always last.  readNames = nSeqs names or NULL.  0 = ok.
+ *   bwamem_hip_bam_record_bytes  tooling: the size of the BAM record of one response record (rec: n_words int32 words starting at
+ *                   its flag/mapq word; k = its index within the read, l_read / l_name = lengths of the read and its name), or
+ *                   a negative error (-1: more than 65 535 CIGAR operations, -2: does not parse). */
+int    bwamem_hip_batch_keep_offsets(bwamem_batch_t* b, int on);
+int    bwamem_hip_batch_encode_bam(bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off);
+size_t bwamem_hip_batch_bam_bytes(const bwamem_batch_t* b);
+int    bwamem_hip_batch_bam_download(bwamem_batch_t* b, void* dst);
+void*  bwamem_hip_bam_header(bwaidx_t* idx, size_t* pBytes);                 /* jnibwa_free */
+void*  bwamem_hip_bgzf_compress(const void* src, size_t n, int level, int n_threads, int with_eof, size_t* pBytes);   /* jnibwa_free */
+int    bwamem_hip_align_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes,
+                               const char* const* readNames, int level, int fd, int write_header);
+int64_t bwamem_hip_bam_record_bytes(const void* rec, size_t n_words, int k, int32_t l_read, int32_t l_name);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
