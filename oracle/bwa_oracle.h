@@ -156,6 +156,11 @@ void  oracle_free(void *p);
 /* ---- per-stage probes used by the kernel-level parity tests ---- */
 /* all SMEM intervals of mem_collect_intv for one 2-bit read; returns count, fills out[4*i..] = x0,x1,size,info */
 int oracle_collect_intv(o_idx_t *idx, const o_opt_t *opt, int len, const uint8_t *seq, uint64_t *out, int cap);
+/* the FM-index primitives over arrays, and what a test needs to know about an opened index (tests/test_units_seed.py) */
+void oracle_test_extend(const o_idx_t *idx, size_t n, const uint64_t *x0, const uint64_t *x1, const uint64_t *size, const int32_t *c, const int32_t *is_back, uint64_t *out);
+void oracle_test_sa(const o_idx_t *idx, size_t n, const uint64_t *k, int64_t *out);
+int oracle_test_contigs(const o_idx_t *idx, int64_t *out, int cap);
+void oracle_test_bwt_info(const o_idx_t *idx, uint64_t *out9);
 /* instrumentation counters accumulated by the oracle */
 typedef struct { uint64_t n_ext, n_lf, n_sa, n_refbases, n_dp_cells, n_reads; } o_counters_t;
 void oracle_counters_reset(void);

@@ -276,3 +276,37 @@ typedef struct { uint64_t x, y; } o_pairx_t;
 #define pairx_lt(a, b) ((a).x < (b).x)
 O_SORT_DECL(pairx, o_pairx_t, pairx_lt)
 void oracle_test_sort_pairs(size_t n, uint64_t *xy) { o_introsort_pairx(n, (o_pairx_t*)xy); }
+
+/* ---- test hooks: the FM-index primitives over arrays (tests/test_units_seed.py) ---- */
+/* out[3i..] = x0, x1, size of ok[c[i]] of o_bwt_extend((x0[i], x1[i], size[i]), is_back[i]) */
+void oracle_test_extend(const o_idx_t *idx, size_t n, const uint64_t *x0, const uint64_t *x1, const uint64_t *size, const int32_t *c, const int32_t *is_back, uint64_t *out)
+{
+	size_t i;
+	for (i = 0; i < n; ++i) {
+		o_intv_t ik, ok[4];
+		ik.x[0] = x0[i]; ik.x[1] = x1[i]; ik.x[2] = size[i]; ik.info = 0;
+		o_bwt_extend(&idx->bwt, &ik, ok, is_back[i]);
+		out[3*i] = ok[c[i]].x[0]; out[3*i+1] = ok[c[i]].x[1]; out[3*i+2] = ok[c[i]].x[2];
+	}
+}
+/* out[i] = o_bwt_sa(k[i]) */
+void oracle_test_sa(const o_idx_t *idx, size_t n, const uint64_t *k, int64_t *out)
+{
+	size_t i;
+	for (i = 0; i < n; ++i) out[i] = (int64_t)o_bwt_sa(&idx->bwt, k[i]);
+}
+/* contigs: out[2i] = offset, out[2i+1] = len; returns n_seqs (cap entries written at most) */
+int oracle_test_contigs(const o_idx_t *idx, int64_t *out, int cap)
+{
+	int i;
+	for (i = 0; i < idx->bns.n_seqs && i < cap; ++i) { out[2*i] = idx->bns.anns[i].offset; out[2*i+1] = idx->bns.anns[i].len; }
+	return idx->bns.n_seqs;
+}
+/* primary, L2[0..4], seq_len, sa_intv, l_pac */
+void oracle_test_bwt_info(const o_idx_t *idx, uint64_t *out9)
+{
+	int i;
+	out9[0] = idx->bwt.primary;
+	for (i = 0; i < 5; ++i) out9[1 + i] = idx->bwt.L2[i];
+	out9[6] = idx->bwt.seq_len; out9[7] = (uint64_t)idx->bwt.sa_intv; out9[8] = (uint64_t)idx->bns.l_pac;
+}

@@ -232,26 +232,12 @@ def test_emu_response_block_grows(emu, oracle, small_genome, monkeypatch):
     _cmp(emu, oracle, img, reads)
 
 
-def test_emu_scan_forms(emu, monkeypatch):
+def test_emu_scan_forms(monkeypatch):
     """launch_scan (k_seed.hip): the one-workgroup form, the two-launch form whose blocks add up the block sums before them,
-    and the three-launch form with a one-wave scan of the sums must all be numpy's exclusive cumsum."""
-    import ctypes
-    import numpy as np
-    scan = emu.dll._Z11launch_scanPvPKiPliS2_
-    scan.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
-    scan.restype = None
-    rng = np.random.default_rng(5)
-    for single_max, fused_max, sizes in (("8192", "2048", (0, 1, 63, 4097)), ("1", "2048", (1, 4095, 4096, 3 * 4096 + 17)), ("1", "1", (4097, 70 * 4096 + 5))):
-        monkeypatch.setenv("BWAMEM_HIP_SCAN_SINGLE_MAX", single_max)
-        monkeypatch.setenv("BWAMEM_HIP_SCAN_FUSED_MAX", fused_max)
-        for n in sizes:
-            x = rng.integers(0, 1 << 20, size=max(n, 1), dtype=np.int32)[:n]
-            x[: n // 2] = rng.integers(0, 2 ** 31 - 1, size=n // 2, dtype=np.int32)       # totals beyond 32 bits
-            out = np.full(n + 1, -1, dtype=np.int64)
-            tmp = np.zeros(n // 4096 + 4, dtype=np.int64)
-            scan(None, x.ctypes.data, out.ctypes.data, n, tmp.ctypes.data)
-            want = np.concatenate([[0], np.cumsum(x.astype(np.int64))])
-            assert (out == want).all(), (single_max, fused_max, n)
+    and the three-launch form with a one-wave scan of the sums must all be numpy's exclusive cumsum (the check itself is shared
+    with the GPU flavour: tests/test_units_seed.py, through the unit wrapper of launch_scan)."""
+    import test_units_seed as S
+    S.check_scan_forms(S.unit_scan(S.Units("emu")), monkeypatch)
 
 
 def test_emu_mate_rescue_list_resized(oracle, small_genome):
