@@ -39,6 +39,8 @@ _lib.jnibwa_free.argtypes = [ctypes.c_void_p]
 _lib.jnibwa_getVersion.restype = ctypes.c_char_p
 _lib.bwamem_hip_align_to_bam.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p,
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int]
+_lib.bwamem_hip_align_to_bam_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                ctypes.c_int, ctypes.c_int]
 
 
 class CouldNotReadImageException(RuntimeError):
@@ -322,10 +324,12 @@ class BwaMemAligner:
         finally:
             self.index.deRefIndex()
 
-    def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s):
+    def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False):
         """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
         `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
-        "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred)."""
+        "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred).
+        device=True: the BGZF blocks are compressed on the device as well (DEFLATE with dynamic Huffman codes; `level` is ignored
+        and libz is not needed)."""
         opts = self._getOpts()
         seqs = [func(e) for e in sequences]
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
@@ -341,7 +345,10 @@ class BwaMemAligner:
         try:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             try:
-                rc = _lib.bwamem_hip_align_to_bam(self.index.indexAddress, opts, pb, buf, len(buf), arr, level, fd, 1)
+                if device:
+                    rc = _lib.bwamem_hip_align_to_bam_device(self.index.indexAddress, opts, pb, buf, len(buf), arr, fd, 1)
+                else:
+                    rc = _lib.bwamem_hip_align_to_bam(self.index.indexAddress, opts, pb, buf, len(buf), arr, level, fd, 1)
             finally:
                 os.close(fd)
         finally:

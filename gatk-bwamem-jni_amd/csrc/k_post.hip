@@ -9,6 +9,7 @@
 #include "dev_common.h"
 #include "kernels.h"
 #include "post_common.h"
+#include "bgzf_deflate.h"
 
 // WAVE_PER_READ = false: one lane per read.  true (tiles of long reads): one wavefront per read -- sixty-four times the waves
 // in flight for this latency-bound stage -- with lane 0 doing the updates and the banded global alignments of region
@@ -192,6 +193,366 @@ __global__ void __launch_bounds__(256) k_bam_emit(BamTile t)
         if (sub < tail) dst[head + 4 * nw + sub] = bam_byte(R, raw, head + 4 * nw + sub);
         o += R.total; at += R.words;
     }
+}
+
+// ------------------------------------------------------------------ BGZF members on the device (bgzf_deflate.h)
+// One workgroup per member; a fixed grid walks the members, so the token scratch is one member's worth per workgroup.
+//   1. CRC-32: every lane a slice, advanced over the rest of the input by x^(8 * bytes) and combined by XOR.
+//   2. LZ77 in windows of BGZ_WIN positions.  Every position of a window looks up one candidate in the hash table (4-byte hash,
+//      latest earlier position) and the run candidate at distance 1; the longer match wins, the run on a tie.  Only after the
+//      whole window has looked, its positions enter the table by atomicMax of the position: the table then holds, per hash, the
+//      last position of all earlier windows whichever lane stored last, so the matches are a function of the input alone.
+//      Greedy token selection over the window: per chunk of 16 positions one lane computes where a token starting at each
+//      position leaves the chunk (backwards), one lane chains the 64 chunks, then the chunks mark their token starts; a
+//      wavefront scan turns the marks into token indices.  Tokens go to the workgroup's scratch in HBM, histograms to LDS.
+//   3. Huffman: the used symbols are ranked by all lanes, one lane per alphabet builds the length-limited code, one lane
+//      run-length-codes the lengths, builds the code-length code and adds up the exact size; stored wins if not larger.
+//   4. The member -- header, block header, tokens, end of block, CRC-32, ISIZE -- is one bit stream: lanes OR their bits into a
+//      staging area of LDS words at offsets from a workgroup scan, and complete words are stored to the slot as dwords.
+#define BGZ_THREADS 256
+#define BGZ_WIN 1024
+#define BGZ_PER_LANE (BGZ_WIN / BGZ_THREADS)
+#define BGZ_CHUNK 16
+#define BGZ_HASH_BITS 13
+#define BGZ_STAGE_DW 1544                  // a round of 1 024 tokens of at most 48 bits, and the carried word
+
+static __device__ inline uint32_t bgz_ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
+static __device__ inline int bgz_hash(uint32_t v) { return (int)((v * 2654435761u) >> (32 - BGZ_HASH_BITS)); }
+// number of equal leading bytes of a and b (a < b), at most maxl; b + maxl is within the member
+static __device__ inline int bgz_match_len(const uint8_t* a, const uint8_t* b, int maxl)
+{
+    int k = 0;
+    while (k + 4 <= maxl) {
+        const uint32_t x = bgz_ld32(a + k) ^ bgz_ld32(b + k);
+        if (x) return k + (__builtin_ctz(x) >> 3);
+        k += 4;
+    }
+    while (k < maxl && a[k] == b[k]) ++k;
+    return k;
+}
+// nb <= 32 bits of v at bit `bit` of the staging area: by any lane / by the one lane that writes alone
+static __device__ inline void bgz_put(int* stage, uint32_t bit, uint32_t v, int nb)
+{
+    if (nb == 0) return;
+    const uint32_t i = bit >> 5, sh = bit & 31;
+    atomicOr(&stage[i], (int)(v << sh));
+    if (sh + nb > 32) atomicOr(&stage[i + 1], (int)(v >> (32 - sh)));
+}
+static __device__ inline void bgz_put1(int* stage, uint32_t& bit, uint32_t v, int nb)
+{
+    const uint32_t i = bit >> 5, sh = bit & 31;
+    stage[i] |= (int)(v << sh);
+    if (sh + nb > 32) stage[i + 1] |= (int)(v >> (32 - sh));
+    bit += nb;
+}
+// after a barrier behind the puts: the complete words of the staging area go to the slot, the last partial word is carried
+static __device__ inline void bgz_flush(int* stage, uint32_t* out_dw, uint32_t& obits, uint32_t cb, int tid)
+{
+    const uint32_t total = (obits & 31) + cb, full = total >> 5;
+    for (uint32_t k = tid; k < full; k += BGZ_THREADS) out_dw[(obits >> 5) + k] = (uint32_t)stage[k];
+    const int carry = stage[full];
+    __syncthreads();
+    for (uint32_t k = tid; k <= full; k += BGZ_THREADS) stage[k] = k == 0 ? carry : 0;
+    obits += cb;
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(BGZ_THREADS) k_bgzf_deflate(const uint8_t* src, int64_t n_total, int n_blocks, uint8_t* slots, int32_t* sizes, uint32_t* tokens)
+{
+    __shared__ int s_hash[1 << BGZ_HASH_BITS];
+    __shared__ uint16_t s_mlen[2][BGZ_WIN], s_mdist[2][BGZ_WIN], s_exit[BGZ_WIN];
+    __shared__ uint16_t s_entry[BGZ_WIN / BGZ_CHUNK], s_cmask[BGZ_WIN / BGZ_CHUNK];
+    __shared__ int s_cbase[BGZ_WIN / BGZ_CHUNK];
+    __shared__ int s_hll[288], s_hd[32], s_hcl[32], s_cnt[3][16];
+    __shared__ uint32_t s_tll[288], s_td[32], s_tcl[32];
+    __shared__ uint8_t s_lenll[288], s_lend[32], s_lencl[32], s_seq[DFL_NLL + DFL_ND + 4];
+    __shared__ uint16_t s_ordll[288], s_parll[2 * 288], s_ordd[32], s_pard[64], s_rle[DFL_NLL + DFL_ND + 4];
+    __shared__ uint32_t s_wll[288], s_wd[32];
+    __shared__ uint32_t s_crc[256], s_red[BGZ_THREADS];
+    __shared__ int s_stage[BGZ_STAGE_DW];
+    __shared__ int s_scan[BGZ_THREADS], s_gp[64];
+    __shared__ int s_next, s_ntok, s_bits, s_mll, s_md, s_total, s_cb, s_dynamic, s_hlit, s_hdist, s_hclen, s_ncl, s_hbits, s_fix[2];
+
+    const int tid = (int)threadIdx.x;
+    uint32_t* toks = tokens + (size_t)blockIdx.x * BGZF_IN;
+    for (int blk = (int)blockIdx.x; blk < n_blocks; blk += (int)gridDim.x) {
+        const int64_t at = (int64_t)blk * BGZF_IN;
+        const int n = (int)(n_total - at < BGZF_IN ? n_total - at : BGZF_IN);
+        const uint8_t* in = src + at;
+        uint32_t* out_dw = (uint32_t*)(slots + (size_t)blk * BGZF_SLOT);
+
+        for (int k = tid; k < 1 << BGZ_HASH_BITS; k += BGZ_THREADS) s_hash[k] = 0;
+        for (int k = tid; k < BGZ_STAGE_DW; k += BGZ_THREADS) s_stage[k] = 0;
+        for (int k = tid; k < 288; k += BGZ_THREADS) { s_hll[k] = 0; s_lenll[k] = 0; }
+        if (tid < 32) { s_hd[tid] = 0; s_hcl[tid] = 0; s_lend[tid] = 0; s_lencl[tid] = 0; }
+        s_crc[tid] = bgz_crc_table_entry((uint32_t)tid);
+        if (tid == 0) { s_next = 0; s_ntok = 0; s_bits = 0; s_mll = 0; s_md = 0; }
+        __syncthreads();
+
+        {   // ---- 1. CRC-32
+            const int per = (n + BGZ_THREADS - 1) / BGZ_THREADS, lo = tid * per, hi = lo + per < n ? lo + per : n;
+            uint32_t x = 0;
+            if (lo < n) {
+                uint32_t c = lo == 0 ? 0xffffffffu : 0u;
+                for (int p = lo; p < hi; ++p) c = s_crc[(c ^ in[p]) & 0xff] ^ (c >> 8);
+                x = bgz_crc_mul(c, bgz_crc_xpow8((uint32_t)(n - hi)));
+            }
+            s_red[tid] = x;
+        }
+
+        // ---- 2. LZ77
+        for (int w0 = 0, par = 0; w0 < n; w0 += BGZ_WIN, par ^= 1) {
+            const int wn = n - w0 < BGZ_WIN ? n - w0 : BGZ_WIN;
+            const bool active = s_next < w0 + wn;                    // (uniform) a token starts in this window
+            int hv[BGZ_PER_LANE];
+#pragma unroll
+            for (int j = 0; j < BGZ_PER_LANE; ++j) {
+                const int i = j * BGZ_THREADS + tid, p = w0 + i;
+                hv[j] = i < wn && p + 4 <= n ? bgz_hash(bgz_ld32(in + p)) : -1;
+                if (!active || i >= wn) continue;
+                const int maxl = n - p < DFL_MAX_MATCH ? n - p : DFL_MAX_MATCH;
+                int bl = 0, bd = 0;
+                if (maxl >= DFL_MIN_MATCH) {
+                    if (hv[j] >= 0) {
+                        const int c = s_hash[hv[j]] - 1;
+                        if (c >= 0 && p - c <= DFL_MAX_DIST) { const int l = bgz_match_len(in + c, in + p, maxl); if (l >= 4) { bl = l; bd = p - c; } }
+                    }
+                    if (p >= 1 && in[p - 1] == in[p]) { const int l = bgz_match_len(in + p - 1, in + p, maxl); if (l >= DFL_MIN_MATCH && l >= bl) { bl = l; bd = 1; } }
+                }
+                s_mlen[par][i] = (uint16_t)bl; s_mdist[par][i] = (uint16_t)bd;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < BGZ_PER_LANE; ++j)
+                if (hv[j] >= 0) atomicMax(&s_hash[hv[j]], w0 + j * BGZ_THREADS + tid + 1);
+            if (active && tid < BGZ_WIN / BGZ_CHUNK) {               // where a token starting at i leaves the chunk
+                const int lo = tid * BGZ_CHUNK, hi = lo + BGZ_CHUNK < wn ? lo + BGZ_CHUNK : wn;
+                for (int i = hi - 1; i >= lo; --i) {
+                    const int l = s_mlen[par][i], nx = i + (l ? l : 1);
+                    s_exit[i] = (uint16_t)(nx >= hi ? nx : s_exit[nx]);
+                }
+            }
+            __syncthreads();
+            if (active && tid == 0) {                                // the chunks a token starts in, and where
+                int e = s_next - w0;
+                for (int c = 0; c * BGZ_CHUNK < wn; ++c) {
+                    const int hi = (c + 1) * BGZ_CHUNK < wn ? (c + 1) * BGZ_CHUNK : wn;
+                    if (e < hi) { s_entry[c] = (uint16_t)e; e = s_exit[e]; } else s_entry[c] = 0xffff;
+                }
+                s_next = w0 + e;
+            }
+            __syncthreads();
+            if (active && tid < BGZ_WIN / BGZ_CHUNK) {               // token starts of the chunk, and the index of its first token
+                const int lo = tid * BGZ_CHUNK, hi = lo + BGZ_CHUNK < wn ? lo + BGZ_CHUNK : wn;
+                const int base = s_ntok;
+                uint32_t mask = 0;
+                if (lo < wn) {
+                    int i = s_entry[tid];
+                    if (i != 0xffff) while (i < hi) { mask |= 1u << (i - lo); const int l = s_mlen[par][i]; i += l ? l : 1; }
+                }
+                const int cnt = __popc(mask);
+                int incl = cnt;
+                for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (tid >= o) incl += u; }
+                s_cmask[tid] = (uint16_t)mask; s_cbase[tid] = base + incl - cnt;
+                if (tid == 63) s_ntok = base + incl;
+            }
+            __syncthreads();
+            if (active) {
+#pragma unroll
+                for (int j = 0; j < BGZ_PER_LANE; ++j) {
+                    const int i = j * BGZ_THREADS + tid, c = i / BGZ_CHUNK, b = i % BGZ_CHUNK;
+                    if (i >= wn) continue;
+                    const uint32_t mask = s_cmask[c];
+                    if (!(mask >> b & 1)) continue;
+                    const int k = s_cbase[c] + __popc(mask & ((1u << b) - 1));
+                    const int l = s_mlen[par][i];
+                    if (l) {
+                        const int d = s_mdist[par][i];
+                        toks[k] = dfl_tok_match(l, d);
+                        atomicAdd(&s_hll[dfl_len_sym(l)], 1); atomicAdd(&s_hd[dfl_dist_sym(d)], 1);
+                    } else {
+                        const uint8_t v = in[w0 + i];
+                        toks[k] = v;
+                        atomicAdd(&s_hll[v], 1);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- 3. Huffman codes
+        if (tid == 0) {
+            s_hll[DFL_EOB] = 1;
+            int used = 0;
+            for (int s = 0; s < DFL_ND; ++s) used += s_hd[s] > 0;
+            s_fix[0] = s_fix[1] = 0;                                   // fewer than two distance symbols: symbols 0 and 1 fill in, unused by any token
+            if (used < 2 && s_hd[0] == 0) { s_hd[0] = 1; s_fix[0] = 1; ++used; }
+            if (used < 2 && s_hd[1] == 0) { s_hd[1] = 1; s_fix[1] = 1; ++used; }
+        }
+        __syncthreads();
+        for (int s = tid; s < DFL_NLL; s += BGZ_THREADS) if (s_hll[s] > 0) { s_ordll[dfl_rank(s_hll, DFL_NLL, s)] = (uint16_t)s; atomicAdd(&s_mll, 1); }
+        if (tid < DFL_ND && s_hd[tid] > 0) { s_ordd[dfl_rank(s_hd, DFL_ND, tid)] = (uint16_t)tid; atomicAdd(&s_md, 1); }
+        __syncthreads();
+        if (tid == 0) { dfl_code_lengths(s_hll, s_ordll, s_mll, DFL_LL_BITS, s_lenll, s_cnt[0], s_wll, s_parll); dfl_assign_codes(s_lenll, DFL_NLL, DFL_LL_BITS, s_cnt[0], s_tll); }
+        if (tid == 64) { dfl_code_lengths(s_hd, s_ordd, s_md, DFL_LL_BITS, s_lend, s_cnt[1], s_wd, s_pard); dfl_assign_codes(s_lend, DFL_ND, DFL_LL_BITS, s_cnt[1], s_td); }
+        __syncthreads();
+        {   // the bits of the tokens and the end-of-block symbol
+            int bits = 0;
+            for (int s = tid; s < DFL_NLL; s += BGZ_THREADS) bits += s_hll[s] * ((int)s_lenll[s] + dfl_len_extra_bits(s));
+            if (tid < DFL_ND) bits += (s_hd[tid] - (tid < 2 ? s_fix[tid] : 0)) * ((int)s_lend[tid] + dfl_dist_extra_bits(tid));
+            if (bits) atomicAdd(&s_bits, bits);
+        }
+        if (tid == 0) {                                              // the block header: lengths, run-length coded (RFC 1951 3.2.7)
+            int hlit = DFL_NLL, hdist = DFL_ND;
+            while (hlit > 257 && !s_lenll[hlit - 1]) --hlit;
+            while (hdist > 1 && !s_lend[hdist - 1]) --hdist;
+            for (int s = 0; s < hlit; ++s) s_seq[s] = s_lenll[s];
+            for (int s = 0; s < hdist; ++s) s_seq[hlit + s] = s_lend[s];
+            const int ncl = dfl_rle_lengths(s_seq, hlit + hdist, s_rle);
+            for (int k = 0; k < ncl; ++k) ++s_hcl[s_rle[k] & 0xff];
+            int m = 0;
+            for (int s = 0; s < DFL_NCL; ++s) m += s_hcl[s] > 0;
+            if (m < 2) { if (s_hcl[0] == 0) { s_hcl[0] = 1; ++m; } if (m < 2) { s_hcl[1] = 1; ++m; } }
+            for (int s = 0; s < DFL_NCL; ++s) if (s_hcl[s] > 0) s_ordd[dfl_rank(s_hcl, DFL_NCL, s)] = (uint16_t)s;
+            dfl_code_lengths(s_hcl, s_ordd, m, DFL_CL_BITS, s_lencl, s_cnt[2], s_wd, s_pard);
+            dfl_assign_codes(s_lencl, DFL_NCL, DFL_CL_BITS, s_cnt[2], s_tcl);
+            int hclen = DFL_NCL;
+            while (hclen > 4 && !s_lencl[dfl_cl_order(hclen - 1)]) --hclen;
+            int hbits = 3 + 5 + 5 + 4 + 3 * hclen;
+            for (int k = 0; k < ncl; ++k) { const int sym = s_rle[k] & 0xff; hbits += (int)s_lencl[sym] + dfl_cl_extra_bits(sym); }
+            s_hlit = hlit; s_hdist = hdist; s_hclen = hclen; s_ncl = ncl; s_hbits = hbits;
+        }
+        __syncthreads();
+
+        // ---- 4. the member
+        if (tid == 0) {
+            const int dyn_bytes = (s_hbits + s_bits + 7) >> 3, stored_bytes = n + 5;
+            const int dynamic = dyn_bytes < stored_bytes;
+            const int member = BGZF_HEAD + (dynamic ? dyn_bytes : stored_bytes) + BGZF_TAIL;
+            s_dynamic = dynamic;
+            uint32_t bit = 0;
+            bgz_put1(s_stage, bit, 0x04088b1fu, 32); bgz_put1(s_stage, bit, 0, 32);            // ID1 ID2 CM FLG, MTIME
+            bgz_put1(s_stage, bit, 0x0006ff00u, 32);                                           // XFL, OS, XLEN
+            bgz_put1(s_stage, bit, 0x00024342u, 32);                                           // 'B' 'C', SLEN
+            bgz_put1(s_stage, bit, (uint32_t)(member - 1), 16);                                // BSIZE
+            if (dynamic) {
+                bgz_put1(s_stage, bit, 1, 1); bgz_put1(s_stage, bit, 2, 2);
+                bgz_put1(s_stage, bit, (uint32_t)(s_hlit - 257), 5); bgz_put1(s_stage, bit, (uint32_t)(s_hdist - 1), 5); bgz_put1(s_stage, bit, (uint32_t)(s_hclen - 4), 4);
+                for (int i = 0; i < s_hclen; ++i) bgz_put1(s_stage, bit, s_lencl[dfl_cl_order(i)], 3);
+                for (int k = 0; k < s_ncl; ++k) {
+                    const int sym = s_rle[k] & 0xff;
+                    const uint32_t e = s_tcl[sym];
+                    bgz_put1(s_stage, bit, e & 0xffff, (int)(e >> 16));
+                    if (sym >= 16) bgz_put1(s_stage, bit, (uint32_t)(s_rle[k] >> 8), dfl_cl_extra_bits(sym));
+                }
+            } else {
+                bgz_put1(s_stage, bit, 1, 1); bgz_put1(s_stage, bit, 0, 2);
+                bit = (bit + 7) & ~7u;
+                bgz_put1(s_stage, bit, (uint32_t)n, 16); bgz_put1(s_stage, bit, ~(uint32_t)n & 0xffff, 16);
+            }
+            s_cb = (int)bit;
+        }
+        __syncthreads();
+        uint32_t obits = 0;
+        bgz_flush(s_stage, out_dw, obits, (uint32_t)s_cb, tid);
+        const int dynamic = s_dynamic, n_items = dynamic ? s_ntok : n;
+        for (int base = 0; base < n_items; base += 4 * BGZ_THREADS) {
+            uint32_t a[4], b[4]; int na[4], nb[4];
+            int mine = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int k = base + 4 * tid + q;
+                a[q] = b[q] = 0; na[q] = nb[q] = 0;
+                if (k >= n_items) continue;
+                if (!dynamic) { a[q] = in[k]; na[q] = 8; }
+                else {
+                    const uint32_t t = toks[k];
+                    if (t & DFL_TOK_MATCH) {
+                        const int l = dfl_tok_len(t), d = dfl_tok_dist(t), ls = dfl_len_sym(l), ds = dfl_dist_sym(d);
+                        const uint32_t el = s_tll[ls], ed = s_td[ds];
+                        const int xl = dfl_len_extra_bits(ls), xd = dfl_dist_extra_bits(ds);
+                        a[q] = (el & 0xffff) | (uint32_t)dfl_len_extra(l, xl) << (el >> 16); na[q] = (int)(el >> 16) + xl;
+                        b[q] = (ed & 0xffff) | (uint32_t)dfl_dist_extra(d, xd) << (ed >> 16); nb[q] = (int)(ed >> 16) + xd;
+                    } else { const uint32_t e = s_tll[t]; a[q] = e & 0xffff; na[q] = (int)(e >> 16); }
+                }
+                mine += na[q] + nb[q];
+            }
+            // exclusive scan of the lanes' bit counts: groups of four lanes by wavefront 0, the rest from LDS
+            s_scan[tid] = mine;
+            __syncthreads();
+            if (tid < 64) {
+                const int g = s_scan[4 * tid] + s_scan[4 * tid + 1] + s_scan[4 * tid + 2] + s_scan[4 * tid + 3];
+                int incl = g;
+                for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (tid >= o) incl += u; }
+                s_gp[tid] = incl - g;
+                if (tid == 63) s_total = incl;
+            }
+            __syncthreads();
+            uint32_t bit = (obits & 31) + (uint32_t)s_gp[tid >> 2];
+            for (int q = 0; q < (tid & 3); ++q) bit += (uint32_t)s_scan[(tid & ~3) + q];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { bgz_put(s_stage, bit, a[q], na[q]); bit += na[q]; bgz_put(s_stage, bit, b[q], nb[q]); bit += nb[q]; }
+            __syncthreads();
+            bgz_flush(s_stage, out_dw, obits, (uint32_t)s_total, tid);
+        }
+        if (tid == 0) {                                              // end of block, CRC-32, ISIZE
+            uint32_t bit = obits & 31;
+            if (dynamic) { const uint32_t e = s_tll[DFL_EOB]; bgz_put1(s_stage, bit, e & 0xffff, (int)(e >> 16)); }
+            bit = (bit + 7) & ~7u;
+            uint32_t crc = 0;
+            for (int k = 0; k < BGZ_THREADS; ++k) crc ^= s_red[k];
+            bgz_put1(s_stage, bit, ~crc, 32); bgz_put1(s_stage, bit, (uint32_t)n, 32);
+            s_cb = (int)(bit - (obits & 31));
+        }
+        __syncthreads();
+        bgz_flush(s_stage, out_dw, obits, (uint32_t)s_cb, tid);
+        if (tid == 0) {
+            if (obits & 31) out_dw[obits >> 5] = (uint32_t)s_stage[0];
+            sizes[blk] = (int32_t)(obits >> 3);
+        }
+        __syncthreads();
+    }
+}
+
+// the members, packed: one workgroup per member copies its slot to the member's offset; one more writes the EOF block
+__global__ void __launch_bounds__(256) k_bgzf_gather(const uint8_t* slots, const int32_t* sizes, const int64_t* off, int n_blocks, int with_eof, uint8_t* out)
+{
+    const int blk = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (blk >= n_blocks) {
+        if (with_eof && tid < BGZF_EOF_BYTES) out[off[n_blocks] + tid] = bgzf_eof_byte(tid);
+        return;
+    }
+    const uint32_t* S = (const uint32_t*)(slots + (size_t)blk * BGZF_SLOT);
+    const uint8_t* s = (const uint8_t*)S;
+    uint8_t* d = out + off[blk];
+    const int n = sizes[blk];
+    int lead = (int)((4 - (off[blk] & 3)) & 3);
+    if (lead > n) lead = n;
+    const int nw = (n - lead) >> 2, tail = n - lead - 4 * nw;
+    if (tid < lead) d[tid] = s[tid];
+    uint32_t* D = (uint32_t*)(d + lead);
+    const int sh = 8 * (lead & 3);
+    for (int w = tid; w < nw; w += 256) {
+        const int k = (lead + 4 * w) >> 2;
+        D[w] = sh ? S[k] >> sh | S[k + 1] << (32 - sh) : S[k];
+    }
+    if (tid < tail) d[lead + 4 * nw + tid] = s[lead + 4 * nw + tid];
+}
+
+int bgzf_grid(int n_cu, int64_t n_blocks)
+{
+    const int64_t g = 4ll * (n_cu > 0 ? n_cu : 256);
+    return (int)(n_blocks < g ? n_blocks : g);
+}
+size_t bgzf_token_bytes(int grid) { return (size_t)grid * BGZF_IN * sizeof(uint32_t); }
+void launch_bgzf_deflate(hipStream_t st, const uint8_t* src, int64_t n, int n_blocks, int grid, uint8_t* slots, int32_t* sizes, uint32_t* tokens)
+{
+    if (n_blocks <= 0) return;
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(BGZ_THREADS), 0, st, src, n, n_blocks, slots, sizes, tokens);
+}
+void launch_bgzf_gather(hipStream_t st, const uint8_t* slots, const int32_t* sizes, const int64_t* off, int n_blocks, bool with_eof, uint8_t* out)
+{
+    hipLaunchKernelGGL(k_bgzf_gather, dim3(n_blocks + 1), dim3(256), 0, st, slots, sizes, off, n_blocks, with_eof ? 1 : 0, out);
 }
 
 void launch_bam_size(hipStream_t st, const BamTile& t)

@@ -33,6 +33,13 @@ void launch_pack(hipStream_t st, const TileView& tv, uint8_t* dst);
 // BAM records of a tile's packed response (bam_encode.h): sizes per read, then -- after a launch_scan over the batch -- the records
 void launch_bam_size(hipStream_t st, const BamTile& t);
 void launch_bam_emit(hipStream_t st, const BamTile& t);
+// BGZF members of src[0, n) (bgzf_deflate.h): member i of input [i * 0xff00, ...) into slots + i * BGZF_SLOT and its size into
+// sizes[i], by `grid` = bgzf_grid(...) workgroups with bgzf_token_bytes(grid) of scratch; then -- after a launch_scan over the
+// sizes -- the members packed into out at off[i], followed by the 28-byte EOF block at off[n_blocks] when asked for
+int bgzf_grid(int n_cu, int64_t n_blocks);
+size_t bgzf_token_bytes(int grid);
+void launch_bgzf_deflate(hipStream_t st, const uint8_t* src, int64_t n, int n_blocks, int grid, uint8_t* slots, int32_t* sizes, uint32_t* tokens);
+void launch_bgzf_gather(hipStream_t st, const uint8_t* slots, const int32_t* sizes, const int64_t* off, int n_blocks, bool with_eof, uint8_t* out);
 
 // paired-end path (k_pe.hip)
 void launch_pestat_cand(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv, int8_t* cand_dir, int64_t* cand_is);

@@ -31,6 +31,7 @@
 #include <cmath>
 #include "bwamem_types.h"
 #include "kernels.h"
+#include "bgzf_deflate.h"
 #include "index_io.h"
 #include "../../include/bwamem_hip.h"
 
@@ -344,6 +345,9 @@ struct OutSink {
     ~OutSink() { if (h_buf) free(h_buf); }
 };
 
+// BGZF members made on the device (bgzf_deflate.h): out holds `bytes` of them, the rest is the compressor's working storage
+struct BgzfBufs { DevBuf slots, sizes, off, scan_tmp, tokens, out; size_t bytes = 0; };
+
 struct bwamem_batch_s {
     bwaidx_s* idx = nullptr;
     uint32_t n_reads = 0;
@@ -360,6 +364,7 @@ struct bwamem_batch_s {
     int64_t read_id0 = 0;                            // of that call
     DevBuf bam, bam_sizes, bam_off, bam_scan_tmp, bam_names, bam_name_off, bam_err;
     size_t bam_bytes = 0;
+    BgzfBufs bgzf;                                   // BGZF members of those records (bwamem_hip_batch_compress_bam)
 };
 
 static const int LOG_TAB_N = 1 << 20;
@@ -1368,7 +1373,7 @@ static bool align_batch_pe(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes
 static void release_tile_outputs(bwamem_batch_s* b)
 {
     for (TileOut& t : b->tiles) { if (t.d && t.owned) (void)hipFree(t.d); if (t.d_off) (void)hipFree(t.d_off); }
-    b->tiles.clear(); b->result_bytes = 0; b->aligned = false; b->bam_bytes = 0;
+    b->tiles.clear(); b->result_bytes = 0; b->aligned = false; b->bam_bytes = 0; b->bgzf.bytes = 0;
 }
 
 // Tiles are independent, and every kernel of a tile ends in a tail of a few long-running reads; several tiles are
@@ -1746,7 +1751,7 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
     HIP_OK(hipSetDevice(ix->device));
     Workspace& ws = ix->ws;
     if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
-    b->bam_bytes = 0;
+    b->bam_bytes = 0; b->bgzf.bytes = 0;
     if (!b->keep_offsets) { fprintf(stderr, "[bwamem_hip] encode_bam: the batch was aligned without bwamem_hip_batch_keep_offsets\n"); return false; }
     if (!b->aligned) { fprintf(stderr, "[bwamem_hip] encode_bam: the batch holds no finished alignment\n"); return false; }
     if ((names == nullptr) != (name_off == nullptr)) { fprintf(stderr, "[bwamem_hip] encode_bam: names and their offsets go together\n"); return false; }
@@ -1824,6 +1829,84 @@ int bwamem_hip_batch_bam_download(bwamem_batch_t* b, void* dst)
         if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
         if (b->bam_bytes && hipMemcpy(dst, b->bam.p, b->bam_bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
         return 0;
+    });
+}
+
+// ---- BGZF members of n bytes resident at d_src (bgzf_deflate.h; kernels next to the BAM kernels): compress into fixed slots,
+// scan the member sizes, pack.  The device of ix is current and its lock held.
+static bool bgzf_device(bwaidx_s* ix, const uint8_t* d_src, size_t n, bool with_eof, BgzfBufs& z)
+{
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    z.bytes = 0;
+    const size_t n_blocks = (n + BGZF_IN - 1) / BGZF_IN;
+    if (n_blocks >= 0x7fffffffu) { fprintf(stderr, "[bwamem_hip] bgzf: too many blocks\n"); return false; }
+    if (n_blocks == 0) {
+        if (!with_eof) return true;
+        uint8_t eof[BGZF_EOF_BYTES];
+        for (int i = 0; i < BGZF_EOF_BYTES; ++i) eof[i] = bgzf_eof_byte(i);
+        if (!z.out.ensure(BGZF_EOF_BYTES)) return false;
+        HIP_OK(hipMemcpy(z.out.p, eof, BGZF_EOF_BYTES, hipMemcpyHostToDevice));
+        z.bytes = BGZF_EOF_BYTES;
+        return true;
+    }
+    const int grid = bgzf_grid(ix->d.n_cu, (int64_t)n_blocks);
+    if (!(z.slots.ensure(n_blocks * BGZF_SLOT + 16) && z.sizes.ensure(n_blocks * 4) && z.off.ensure((n_blocks + 1) * 8)
+          && z.scan_tmp.ensure(scan_tmp_bytes((int64_t)n_blocks + 1)) && z.tokens.ensure(bgzf_token_bytes(grid)))) return false;
+    TIMED(ws, K_OTHER, launch_bgzf_deflate(ws.stream, d_src, (int64_t)n, (int)n_blocks, grid, z.slots.as<uint8_t>(), z.sizes.as<int32_t>(), z.tokens.as<uint32_t>()));
+    launch_scan(ws.stream, z.sizes.as<int32_t>(), z.off.as<int64_t>(), (int)n_blocks, z.scan_tmp.as<int64_t>());
+    HIP_OK(hipGetLastError());
+    int64_t total = 0;
+    HIP_OK(hipMemcpyAsync(&total, z.off.as<int64_t>() + n_blocks, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
+    if (total < (int64_t)n_blocks * (BGZF_HEAD + BGZF_TAIL) || (uint64_t)total > (uint64_t)n_blocks * BGZF_SLOT) { fprintf(stderr, "[bwamem_hip] bgzf: internal error: member sizes do not add up\n"); return false; }
+    if (!z.out.ensure((size_t)total + BGZF_EOF_BYTES)) return false;
+    TIMED(ws, K_OTHER, launch_bgzf_gather(ws.stream, z.slots.as<uint8_t>(), z.sizes.as<int32_t>(), z.off.as<int64_t>(), (int)n_blocks, with_eof, z.out.as<uint8_t>()));
+    HIP_OK(hipStreamSynchronize(ws.stream));
+    timed_collect(ws);
+    z.bytes = (size_t)total + (with_eof ? BGZF_EOF_BYTES : 0);
+    return true;
+}
+
+int bwamem_hip_batch_compress_bam(bwamem_batch_t* b, int with_eof)
+{
+    return guarded("bwamem_hip_batch_compress_bam", -1, [&]() -> int {
+        if (!b || !b->idx) return -1;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        b->bgzf.bytes = 0;
+        if (b->bam_bytes == 0) return -1;
+        if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+        return bgzf_device(b->idx, b->bam.as<uint8_t>(), b->bam_bytes, with_eof != 0, b->bgzf) ? 0 : -1;
+    });
+}
+
+size_t bwamem_hip_batch_bgzf_bytes(const bwamem_batch_t* b) { return b ? b->bgzf.bytes : 0; }
+
+int bwamem_hip_batch_bgzf_download(bwamem_batch_t* b, void* dst)
+{
+    return guarded("bwamem_hip_batch_bgzf_download", -1, [&]() -> int {
+        if (!b || (!dst && b->bgzf.bytes)) return -1;
+        if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+        if (b->bgzf.bytes && hipMemcpy(dst, b->bgzf.out.p, b->bgzf.bytes, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        return 0;
+    });
+}
+
+void* bwamem_hip_bgzf_compress_device(bwaidx_t* idx, const void* src, size_t n, int with_eof, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    return guarded("bwamem_hip_bgzf_compress_device", (void*)0, [&]() -> void* {
+        if (!idx || (n && !src)) return nullptr;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (hipSetDevice(idx->device) != hipSuccess) return nullptr;
+        DevBuf in; BgzfBufs z;
+        if (n) { if (!in.ensure(n) || hipMemcpy(in.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return nullptr; }
+        if (!bgzf_device(idx, in.as<uint8_t>(), n, with_eof != 0, z)) return nullptr;
+        void* res = malloc(z.bytes ? z.bytes : 1);
+        if (!res) return nullptr;
+        if (z.bytes && hipMemcpy(res, z.out.p, z.bytes, hipMemcpyDeviceToHost) != hipSuccess) { free(res); return nullptr; }
+        if (pBytes) *pBytes = z.bytes;
+        return res;
     });
 }
 

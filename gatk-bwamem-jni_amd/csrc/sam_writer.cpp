@@ -377,4 +377,39 @@ int bwamem_hip_align_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pesta
     } catch (...) { return -1; }
 }
 
+// bwamem_hip_align_to_bam with the BGZF members made on the device: only compressed bytes are downloaded, and libz is not touched
+int bwamem_hip_align_to_bam_device(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
+                                   int fd, int write_header)
+{
+    try {
+        if (!idx || !opt || !pSeq || nBytes < 4 || fd < 0) return -1;
+        uint32_t n_reads; memcpy(&n_reads, pSeq, 4);
+        int32_t flag; memcpy(&flag, (const char*)opt + 60, 4);                  // mem_opt_t.flag (BwaMemAligner.java:75)
+        const int paired = (flag & 0x2) != 0;
+        std::string blob; std::vector<int64_t> name_off;
+        if (readNames) {
+            name_off.reserve((size_t)n_reads + 1);
+            for (uint32_t i = 0; i < n_reads; ++i) { name_off.push_back((int64_t)blob.size()); if (readNames[i]) blob += readNames[i]; }
+            name_off.push_back((int64_t)blob.size());
+        }
+        BatchOwner bo{ bwamem_hip_batch_upload(idx, pSeq, nBytes) };
+        if (!bo.b) return -1;
+        if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
+        if (bwamem_hip_batch_encode_bam(bo.b, paired, readNames ? blob.data() : nullptr, readNames ? name_off.data() : nullptr) != 0) return -1;
+        if (write_header) {
+            size_t nh = 0, nz = 0;
+            Freed hdr(bwamem_hip_bam_header(idx, &nh));
+            if (!hdr.p) return -1;
+            Freed z(bwamem_hip_bgzf_compress_device(idx, hdr.p, nh, 0, &nz));
+            if (!z.p || !write_all(fd, (const uint8_t*)z.p, nz)) return -1;
+        }
+        if (bwamem_hip_batch_bam_bytes(bo.b) == 0) return write_all(fd, BGZF_EOF, sizeof BGZF_EOF) ? 0 : -1;      // no record: the EOF block alone
+        if (bwamem_hip_batch_compress_bam(bo.b, 1) != 0) return -1;
+        const size_t nz = bwamem_hip_batch_bgzf_bytes(bo.b);
+        Freed z(malloc(nz ? nz : 1));
+        if (!z.p || bwamem_hip_batch_bgzf_download(bo.b, z.p) != 0 || !write_all(fd, (const uint8_t*)z.p, nz)) return -1;
+        return 0;
+    } catch (...) { return -1; }
+}
+
 }  // extern "C"

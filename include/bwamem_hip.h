@@ -141,6 +141,22 @@ int    bwamem_hip_align_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pe
                                const char* const* readNames, int level, int fd, int write_header);
 int64_t bwamem_hip_bam_record_bytes(const void* rec, size_t n_words, int k, int32_t l_read, int32_t l_name);
 
+/* BGZF on the device (csrc/bgzf_deflate.h; additive): the members are compressed by HIP kernels -- LZ77 matching, dynamic Huffman
+ * codes, CRC-32 -- one workgroup per block of at most 0xff00 input bytes, so only compressed bytes cross to the host, libz is not
+ * needed and no host thread compresses.  The bytes are a function of the input alone.
+ *   _compress_bam   after _encode_bam: the BGZF members of the records (with_eof: followed by the EOF block), in a device buffer
+ *                   owned by the batch.  Non-zero (and 0 bytes) without encoded records.  _encode_bam and a new alignment of
+ *                   the batch discard the members.
+ *   _bgzf_bytes / _bgzf_download   their size, and their copy to host memory
+ *   bwamem_hip_bgzf_compress_device   host bytes in, BGZF out (jnibwa_free): upload, the same kernels, download; idx selects the device
+ *   bwamem_hip_align_to_bam_device    bwamem_hip_align_to_bam with the header block and the records compressed on the device */
+int    bwamem_hip_batch_compress_bam(bwamem_batch_t* b, int with_eof);
+size_t bwamem_hip_batch_bgzf_bytes(const bwamem_batch_t* b);
+int    bwamem_hip_batch_bgzf_download(bwamem_batch_t* b, void* dst);
+void*  bwamem_hip_bgzf_compress_device(bwaidx_t* idx, const void* src, size_t n, int with_eof, size_t* pBytes);
+int    bwamem_hip_align_to_bam_device(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes,
+                                      const char* const* readNames, int fd, int write_header);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
