@@ -41,6 +41,8 @@ _lib.bwamem_hip_align_to_bam.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctype
                                          ctypes.c_int, ctypes.c_int, ctypes.c_int]
 _lib.bwamem_hip_align_to_bam_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p,
                                                 ctypes.c_int, ctypes.c_int]
+_lib.bwamem_hip_align_to_sorted_bam.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int]
 
 
 class CouldNotReadImageException(RuntimeError):
@@ -324,12 +326,16 @@ class BwaMemAligner:
         finally:
             self.index.deRefIndex()
 
-    def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False):
+    def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False, sort=False, index_path=None):
         """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
         `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
         "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred).
         device=True: the BGZF blocks are compressed on the device as well (DEFLATE with dynamic Huffman codes; `level` is ignored
-        and libz is not needed)."""
+        and libz is not needed).
+        sort=True (implies device=True): the records are coordinate-sorted on the device within this call and the header says
+        SO:coordinate; index_path: the BAI index of that file is written there as well (needs sort=True)."""
+        if index_path is not None and not sort:
+            raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
         opts = self._getOpts()
         seqs = [func(e) for e in sequences]
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
@@ -345,7 +351,14 @@ class BwaMemAligner:
         try:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             try:
-                if device:
+                if sort:
+                    fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
+                    try:
+                        rc = _lib.bwamem_hip_align_to_sorted_bam(self.index.indexAddress, opts, pb, buf, len(buf), arr, fd, fd_bai, 1)
+                    finally:
+                        if fd_bai >= 0:
+                            os.close(fd_bai)
+                elif device:
                     rc = _lib.bwamem_hip_align_to_bam_device(self.index.indexAddress, opts, pb, buf, len(buf), arr, fd, 1)
                 else:
                     rc = _lib.bwamem_hip_align_to_bam(self.index.indexAddress, opts, pb, buf, len(buf), arr, level, fd, 1)

@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "post_common.h"
 #include "bgzf_deflate.h"
+#include "bam_sort.h"
 
 // WAVE_PER_READ = false: one lane per read.  true (tiles of long reads): one wavefront per read -- sixty-four times the waves
 // in flight for this latency-bound stage -- with lane 0 doing the updates and the banded global alignments of region
@@ -537,6 +538,284 @@ __global__ void __launch_bounds__(256) k_bgzf_gather(const uint8_t* slots, const
         D[w] = sh ? S[k] >> sh | S[k + 1] << (32 - sh) : S[k];
     }
     if (tid < tail) d[lead + 4 * nw + tid] = s[lead + 4 * nw + tid];
+}
+
+// ------------------------------------------------------------------ stable radix sort of (key, index) pairs (bam_sort.h)
+// the lanes' words of SortBits, OR-ed over the wavefront, then into bits[] by one lane per wavefront (every lane of the
+// workgroup calls this)
+static __device__ inline void sort_bits_flush(const int32_t* w, int32_t* bits)
+{
+    for (int k = 0; k <= SORT_BITS_HAS_OTHER; ++k) {
+        int v = w[k];
+        for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o);
+        if (((int)threadIdx.x & 63) == 0 && v) atomicOr(&bits[k], v);
+    }
+}
+
+__global__ void __launch_bounds__(SORT_THREADS) k_sort_bits(const uint64_t* keys, int64_t n, int32_t* bits)
+{
+    int32_t w[SORT_BITS_N];
+    for (int k = 0; k < SORT_BITS_N; ++k) w[k] = 0;
+    const int64_t step = (int64_t)gridDim.x * SORT_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * SORT_THREADS + (int)threadIdx.x; i < n; i += step) sort_bits_add(keys[i], w);
+    sort_bits_flush(w, bits);
+}
+
+// step 1 of a pass: the tile's count of every digit, digit-major
+__global__ void __launch_bounds__(SORT_THREADS) k_sort_hist(const uint64_t* keys, int64_t n, int byte, int n_tiles, int32_t* hist)
+{
+    __shared__ int s_h[SORT_RADIX];
+    const int tid = (int)threadIdx.x;
+    s_h[tid] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * SORT_TILE;
+    for (int j = 0; j < SORT_ITEMS; ++j) {
+        const int64_t i = base + j * SORT_THREADS + tid;
+        if (i < n) atomicAdd(&s_h[sort_digit(keys[i], byte)], 1);
+    }
+    __syncthreads();
+    hist[(int64_t)tid * n_tiles + (int)blockIdx.x] = s_h[tid];
+}
+
+// step 3: the stable scatter.  off = the scan of hist; idx == null: the identity (the first pass)
+__global__ void __launch_bounds__(SORT_THREADS) k_sort_scatter(const uint64_t* keys, const uint32_t* idx, int64_t n, int byte, int n_tiles, const int64_t* off,
+                                                               uint64_t* keys_out, uint32_t* idx_out)
+{
+    __shared__ uint16_t s_cnt[SORT_ITEMS * (SORT_THREADS / 64)][SORT_RADIX];      // per (item, wave): the count of every digit, then its exclusive prefix
+    __shared__ int64_t s_base[SORT_RADIX];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int k = 0; k < SORT_ITEMS * (SORT_THREADS / 64); ++k) s_cnt[k][tid] = 0;
+    s_base[tid] = off[(int64_t)tid * n_tiles + (int)blockIdx.x];
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * SORT_TILE;
+    uint64_t key[SORT_ITEMS];
+    int rank[SORT_ITEMS];
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; ++j) {
+        const int64_t i = base + j * SORT_THREADS + tid;
+        const bool valid = i < n;
+        key[j] = valid ? keys[i] : 0;
+        const int d = sort_digit(key[j], byte);
+        unsigned long long same = __ballot(valid);                    // the lanes of the wave that hold the same digit
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long set = __ballot(d >> bit & 1);
+            same &= (d >> bit & 1) ? set : ~set;
+        }
+        rank[j] = __popcll(same & ((1ull << lane) - 1));
+        if (valid && rank[j] == 0) s_cnt[j * (SORT_THREADS / 64) + wv][d] = (uint16_t)__popcll(same);
+    }
+    __syncthreads();
+    {   // lane = digit: the groups before each (item, wave) group
+        int run = 0;
+        for (int k = 0; k < SORT_ITEMS * (SORT_THREADS / 64); ++k) { const int c = s_cnt[k][tid]; s_cnt[k][tid] = (uint16_t)run; run += c; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; ++j) {
+        const int64_t i = base + j * SORT_THREADS + tid;
+        if (i >= n) continue;
+        const int d = sort_digit(key[j], byte);
+        const int64_t at = s_base[d] + s_cnt[j * (SORT_THREADS / 64) + wv][d] + rank[j];
+        keys_out[at] = key[j];
+        idx_out[at] = idx ? idx[i] : (uint32_t)i;
+    }
+}
+
+// ------------------------------------------------------------------ coordinate-sorted BAM records (bam_sort.h)
+// step 1: one lane per read walks the read's records along block_size and counts them; the OR / AND of their keys on the way
+__global__ void __launch_bounds__(64) k_bamrec_count(const uint8_t* bam, const int64_t* bam_off, int n_reads, int32_t* counts, int32_t* bits, int32_t* err)
+{
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    int32_t w[SORT_BITS_N];
+    for (int k = 0; k < SORT_BITS_N; ++k) w[k] = 0;
+    if (r < n_reads) {
+        int64_t o = bam_off[r];
+        const int64_t hi = bam_off[r + 1];
+        int32_t cnt = 0;
+        bool bad = false;
+        while (o < hi) {
+            if (hi - o < BAMSORT_MIN_REC) { bad = true; break; }
+            const int64_t size = 4 + (int64_t)(int32_t)bamsort_ld32(bam + o);
+            if (size < BAMSORT_MIN_REC || size > hi - o) { bad = true; break; }
+            sort_bits_add(bamsort_key(bam + o), w);
+            ++cnt; o += size;
+        }
+        counts[r] = bad ? 0 : cnt;
+        if (bad) atomicOr(err, BAMSORT_ERR_WALK);
+    }
+    sort_bits_flush(w, bits);
+}
+
+// step 2 (after the scan of the counts): key, place and size of every record, in response order
+__global__ void __launch_bounds__(64) k_bamrec_keys(const uint8_t* bam, const int64_t* bam_off, int n_reads, const int64_t* first, uint64_t* keys, int64_t* src_off, int32_t* sizes)
+{
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= n_reads) return;
+    int64_t o = bam_off[r];
+    const int64_t k0 = first[r], k1 = first[r + 1];
+    for (int64_t k = k0; k < k1; ++k) {
+        const int32_t size = 4 + (int32_t)bamsort_ld32(bam + o);
+        keys[k] = bamsort_key(bam + o); src_off[k] = o; sizes[k] = size;
+        o += size;
+    }
+}
+
+// the sizes in sorted order (their scan gives the records' places in the sorted stream)
+__global__ void __launch_bounds__(256) k_bamrec_sizes(const uint32_t* idx, const int32_t* sizes, int n, int32_t* out)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n) out[i] = sizes[idx[i]];
+}
+
+// the gather, balanced by bytes: every workgroup fills BAMSORT_CHUNK bytes of the destination.  One lane finds the records
+// that overlap the chunk (their places are ascending), the workgroup loads their bounds into LDS, and every lane then looks
+// up the record of each of its dwords there.  A dword inside one record is one load and one store; a dword across a
+// boundary, and the tail of the stream, go byte by byte.
+__global__ void __launch_bounds__(256) k_bamrec_gather(const uint8_t* src, const int64_t* src_off, const uint32_t* idx, const int64_t* dst_off, int n_rec, int64_t total, uint8_t* dst)
+{
+    __shared__ int64_t s_src[BAMSORT_CHUNK_RECS];
+    __shared__ int32_t s_dst[BAMSORT_CHUNK_RECS + 1];
+    __shared__ int s_r0, s_n;
+    const int tid = (int)threadIdx.x;
+    const int64_t lo = (int64_t)blockIdx.x * BAMSORT_CHUNK, hi = total - lo < BAMSORT_CHUNK ? total : lo + BAMSORT_CHUNK;
+    if (tid == 0) {
+        int a = 0, b = n_rec - 1;                                    // the last record that starts at or before lo
+        while (a < b) { const int m = (int)(((int64_t)a + b + 1) >> 1); if (dst_off[m] <= lo) a = m; else b = m - 1; }
+        int c = a, e = n_rec - 1;                                    // the last record that starts before hi
+        while (c < e) { const int m = (int)(((int64_t)c + e + 1) >> 1); if (dst_off[m] < hi) c = m; else e = m - 1; }
+        s_r0 = a;
+        s_n = c - a + 1 < BAMSORT_CHUNK_RECS ? c - a + 1 : BAMSORT_CHUNK_RECS;    // (records of at least BAMSORT_MIN_REC bytes: never more)
+    }
+    __syncthreads();
+    const int r0 = s_r0, nr = s_n;
+    for (int k = tid; k < nr; k += 256) { s_src[k] = src_off[idx[r0 + k]]; s_dst[k] = (int32_t)(dst_off[r0 + k] - lo); }
+    if (tid == 0) s_dst[nr] = (int32_t)(dst_off[r0 + nr] - lo);
+    __syncthreads();
+    int len = (int)(hi - lo);
+    if (len > s_dst[nr]) len = s_dst[nr];
+    for (int x = 4 * tid; x < len; x += 4 * 256) {
+        int a = 0, b = nr - 1;                                       // the record of byte x
+        while (a < b) { const int m = (a + b + 1) >> 1; if (s_dst[m] <= x) a = m; else b = m - 1; }
+        if (x + 4 <= len && x + 4 <= s_dst[a + 1]) *(uint32_t*)(dst + lo + x) = bamsort_ld32(src + s_src[a] + (x - s_dst[a]));
+        else
+            for (int q = 0; q < 4 && x + q < len; ++q) {
+                while (a + 1 < nr && s_dst[a + 1] <= x + q) ++a;
+                dst[lo + x + q] = src[s_src[a] + (x + q - s_dst[a])];
+            }
+    }
+}
+
+// ------------------------------------------------------------------ the BAI index of the sorted, compressed records (bam_sort.h)
+// one lane per record: the bin key, the windows the record overlaps, the count of unplaced records
+__global__ void __launch_bounds__(64) k_bai_records(BaiView v)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    bool unplaced = false;
+    if (i < v.n_rec) {
+        const uint8_t* rec = v.bam + v.rec_off[i];
+        const int64_t size = v.rec_off[i + 1] - v.rec_off[i];
+        const int32_t refid = (int32_t)bamsort_ld32(rec + 4), pos = (int32_t)bamsort_ld32(rec + 8);
+        uint64_t key = SORT_KEY_LAST;
+        if (refid == -1) unplaced = true;
+        else if (refid < 0 || refid >= v.n_ref || pos < 0) atomicOr(v.err, BAMSORT_ERR_WALK);
+        else {
+            const uint32_t bmq = bamsort_ld32(rec + 12), fnc = bamsort_ld32(rec + 16);
+            const int64_t l_name = bmq & 0xff, n_cig = fnc & 0xffff;
+            if (36 + l_name + 4 * n_cig > size) atomicOr(v.err, BAMSORT_ERR_WALK);
+            else {
+                const uint8_t* cig = rec + 36 + l_name;
+                int64_t span = 0;
+                for (int64_t c = 0; c < n_cig; ++c) {
+                    const uint32_t x = bamsort_ld32(cig + 4 * c), op = x & 0xf;
+                    if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += x >> 4;
+                }
+                const int64_t end = (int64_t)pos + (span > 0 ? span : 1);
+                const int32_t w0 = v.win_base[refid], n_win = v.win_base[refid + 1] - w0;
+                key = (uint64_t)(uint32_t)refid << 32 | (bmq >> 16);
+                if (end > BAI_MAX_END) atomicOr(v.err, BAMSORT_ERR_END);
+                else if ((end - 1) >> BAI_WINDOW_SHIFT >= n_win) atomicOr(v.err, BAMSORT_ERR_WINDOW);
+                else for (int64_t w = pos >> BAI_WINDOW_SHIFT; w <= (end - 1) >> BAI_WINDOW_SHIFT; ++w) atomicMax(&v.win[w0 + w], v.n_rec - 1 - i);
+            }
+        }
+        v.keys[i] = key;
+    }
+    const int c = __popcll(__ballot(unplaced));
+    if (((int)threadIdx.x & 63) == 0 && c) atomicAdd(v.n_no_coor, c);
+}
+
+// positions of the (refID, bin)-sorted list at which a chunk starts
+__global__ void __launch_bounds__(256) k_bai_mark(const uint64_t* keys, const uint32_t* idx, int n, int32_t* start)
+{
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (j < n) start[j] = j == 0 || keys[j] != keys[j - 1] || idx[j] != idx[j - 1] + 1;
+}
+
+// the chunks, compacted: cid = the scan of start
+__global__ void __launch_bounds__(256) k_bai_chunks(const uint64_t* keys, const uint32_t* idx, int n, const int32_t* start, const int64_t* cid, const int64_t* rec_off,
+                                                    const int64_t* member_off, int64_t coffset0, BaiChunk* out)
+{
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (j >= n) return;
+    const int64_t c = cid[j] + start[j] - 1;
+    if (start[j]) { out[c].key = keys[j]; out[c].beg = bai_voffset(member_off, coffset0, rec_off[idx[j]]); }
+    if (j == n - 1 || start[j + 1]) out[c].end = bai_voffset(member_off, coffset0, rec_off[idx[j] + 1]);
+}
+
+// the windows' smallest record index as that record's virtual offset (SORT_KEY_LAST: no record)
+__global__ void __launch_bounds__(256) k_bai_windows(const int32_t* win, int n_win, int n_rec, const int64_t* rec_off, const int64_t* member_off, int64_t coffset0, uint64_t* out)
+{
+    const int w = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (w < n_win) out[w] = win[w] < 0 ? SORT_KEY_LAST : bai_voffset(member_off, coffset0, rec_off[n_rec - 1 - win[w]]);
+}
+
+void launch_sort_bits(hipStream_t st, const uint64_t* keys, int64_t n, int32_t* bits)
+{
+    if (n <= 0) return;
+    const int64_t g = (n + SORT_TILE - 1) / SORT_TILE;
+    hipLaunchKernelGGL(k_sort_bits, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(SORT_THREADS), 0, st, keys, n, bits);
+}
+void launch_sort_hist(hipStream_t st, const uint64_t* keys, int64_t n, int byte, int32_t* hist)
+{
+    const int nt = (int)sort_n_tiles(n);
+    hipLaunchKernelGGL(k_sort_hist, dim3(nt), dim3(SORT_THREADS), 0, st, keys, n, byte, nt, hist);
+}
+void launch_sort_scatter(hipStream_t st, const uint64_t* keys, const uint32_t* idx, int64_t n, int byte, const int64_t* off, uint64_t* keys_out, uint32_t* idx_out)
+{
+    const int nt = (int)sort_n_tiles(n);
+    hipLaunchKernelGGL(k_sort_scatter, dim3(nt), dim3(SORT_THREADS), 0, st, keys, idx, n, byte, nt, off, keys_out, idx_out);
+}
+void launch_bamrec_count(hipStream_t st, const uint8_t* bam, const int64_t* bam_off, int n_reads, int32_t* counts, int32_t* bits, int32_t* err)
+{
+    hipLaunchKernelGGL(k_bamrec_count, dim3((n_reads + 63) / 64), dim3(64), 0, st, bam, bam_off, n_reads, counts, bits, err);
+}
+void launch_bamrec_keys(hipStream_t st, const uint8_t* bam, const int64_t* bam_off, int n_reads, const int64_t* first, uint64_t* keys, int64_t* src_off, int32_t* sizes)
+{
+    hipLaunchKernelGGL(k_bamrec_keys, dim3((n_reads + 63) / 64), dim3(64), 0, st, bam, bam_off, n_reads, first, keys, src_off, sizes);
+}
+void launch_bamrec_sizes(hipStream_t st, const uint32_t* idx, const int32_t* sizes, int n, int32_t* out)
+{
+    hipLaunchKernelGGL(k_bamrec_sizes, dim3((n + 255) / 256), dim3(256), 0, st, idx, sizes, n, out);
+}
+void launch_bamrec_gather(hipStream_t st, const uint8_t* src, const int64_t* src_off, const uint32_t* idx, const int64_t* dst_off, int n_rec, int64_t total, uint8_t* dst)
+{
+    hipLaunchKernelGGL(k_bamrec_gather, dim3((unsigned)((total + BAMSORT_CHUNK - 1) / BAMSORT_CHUNK)), dim3(256), 0, st, src, src_off, idx, dst_off, n_rec, total, dst);
+}
+void launch_bai_records(hipStream_t st, const BaiView& v)
+{
+    hipLaunchKernelGGL(k_bai_records, dim3((v.n_rec + 63) / 64), dim3(64), 0, st, v);
+}
+void launch_bai_mark(hipStream_t st, const uint64_t* keys, const uint32_t* idx, int n, int32_t* start)
+{
+    hipLaunchKernelGGL(k_bai_mark, dim3((n + 255) / 256), dim3(256), 0, st, keys, idx, n, start);
+}
+void launch_bai_chunks(hipStream_t st, const uint64_t* keys, const uint32_t* idx, int n, const int32_t* start, const int64_t* cid, const int64_t* rec_off,
+                       const int64_t* member_off, int64_t coffset0, BaiChunk* out)
+{
+    hipLaunchKernelGGL(k_bai_chunks, dim3((n + 255) / 256), dim3(256), 0, st, keys, idx, n, start, cid, rec_off, member_off, coffset0, out);
+}
+void launch_bai_windows(hipStream_t st, const int32_t* win, int n_win, int n_rec, const int64_t* rec_off, const int64_t* member_off, int64_t coffset0, uint64_t* out)
+{
+    hipLaunchKernelGGL(k_bai_windows, dim3((n_win + 255) / 256), dim3(256), 0, st, win, n_win, n_rec, rec_off, member_off, coffset0, out);
 }
 
 int bgzf_grid(int n_cu, int64_t n_blocks)

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "bwamem_types.h"
 #include "bam_encode.h"
+#include "bam_sort.h"
 
 void launch_build_occ64(hipStream_t st, const uint32_t* bwt, uint64_t n_blocks, uint4* occ);
 // suffix array at every ix.sa_intv-th rank (lo/hi, (seq_len >> sa_shift) + 1 entries) from the image's sampling; *err: device int, OR-ed on failure
@@ -40,6 +41,26 @@ int bgzf_grid(int n_cu, int64_t n_blocks);
 size_t bgzf_token_bytes(int grid);
 void launch_bgzf_deflate(hipStream_t st, const uint8_t* src, int64_t n, int n_blocks, int grid, uint8_t* slots, int32_t* sizes, uint32_t* tokens);
 void launch_bgzf_gather(hipStream_t st, const uint8_t* slots, const int32_t* sizes, const int64_t* off, int n_blocks, bool with_eof, uint8_t* out);
+// Stable LSD radix sort of n (64-bit key, 32-bit index) pairs (bam_sort.h).  _bits: the OR / AND words of the keys into bits
+// (SORT_BITS_N ints, zeroed by the caller; sort_live_bytes names the passes to run).  One pass over byte `byte`: _hist into hist
+// (256 * sort_n_tiles(n) ints), launch_scan over them, _scatter from (keys, idx) to (keys_out, idx_out); idx == null: the identity.
+void launch_sort_bits(hipStream_t st, const uint64_t* keys, int64_t n, int32_t* bits);
+void launch_sort_hist(hipStream_t st, const uint64_t* keys, int64_t n, int byte, int32_t* hist);
+void launch_sort_scatter(hipStream_t st, const uint64_t* keys, const uint32_t* idx, int64_t n, int byte, const int64_t* off, uint64_t* keys_out, uint32_t* idx_out);
+// Coordinate-sorted records: _count the records of every read (and the OR / AND words of their keys), after a launch_scan _keys
+// writes key, place and size of every record; after the sort _sizes permutes the sizes, and after their scan _gather copies the
+// records to their places in dst (total bytes)
+void launch_bamrec_count(hipStream_t st, const uint8_t* bam, const int64_t* bam_off, int n_reads, int32_t* counts, int32_t* bits, int32_t* err);
+void launch_bamrec_keys(hipStream_t st, const uint8_t* bam, const int64_t* bam_off, int n_reads, const int64_t* first, uint64_t* keys, int64_t* src_off, int32_t* sizes);
+void launch_bamrec_sizes(hipStream_t st, const uint32_t* idx, const int32_t* sizes, int n, int32_t* out);
+void launch_bamrec_gather(hipStream_t st, const uint8_t* src, const int64_t* src_off, const uint32_t* idx, const int64_t* dst_off, int n_rec, int64_t total, uint8_t* dst);
+// The BAI index: bin keys and windows per record; the chunk starts of the (refID, bin)-sorted list and -- after a launch_scan -- the
+// chunks; the windows' first records as virtual offsets
+void launch_bai_records(hipStream_t st, const BaiView& v);
+void launch_bai_mark(hipStream_t st, const uint64_t* keys, const uint32_t* idx, int n, int32_t* start);
+void launch_bai_chunks(hipStream_t st, const uint64_t* keys, const uint32_t* idx, int n, const int32_t* start, const int64_t* cid, const int64_t* rec_off,
+                       const int64_t* member_off, int64_t coffset0, BaiChunk* out);
+void launch_bai_windows(hipStream_t st, const int32_t* win, int n_win, int n_rec, const int64_t* rec_off, const int64_t* member_off, int64_t coffset0, uint64_t* out);
 
 // paired-end path (k_pe.hip)
 void launch_pestat_cand(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv, int8_t* cand_dir, int64_t* cand_is);

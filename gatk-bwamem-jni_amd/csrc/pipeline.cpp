@@ -347,6 +347,8 @@ struct OutSink {
 
 // BGZF members made on the device (bgzf_deflate.h): out holds `bytes` of them, the rest is the compressor's working storage
 struct BgzfBufs { DevBuf slots, sizes, off, scan_tmp, tokens, out; size_t bytes = 0; };
+// the two sides of the radix sort (bam_sort.h) and its histograms
+struct SortBufs { DevBuf keys[2], idx[2], hist, hist_off, scan_tmp, bits; };
 
 struct bwamem_batch_s {
     bwaidx_s* idx = nullptr;
@@ -365,6 +367,12 @@ struct bwamem_batch_s {
     DevBuf bam, bam_sizes, bam_off, bam_scan_tmp, bam_names, bam_name_off, bam_err;
     size_t bam_bytes = 0;
     BgzfBufs bgzf;                                   // BGZF members of those records (bwamem_hip_batch_compress_bam)
+    // the records coordinate-sorted (bwamem_hip_batch_sort_bam, bam_sort.h): bam then holds them, and rec_dst their places
+    bool bam_encoded = false, bam_sorted = false;    // encoded: _encode_bam succeeded for the resident results (possibly with no record)
+    size_t bam_n_rec = 0;                            // records of the sorted stream
+    DevBuf bam2, rec_cnt, rec_first, rec_src, rec_size, rec_psize, rec_dst, rec_scan_tmp;
+    SortBufs srt;
+    DevBuf bai_win_base, bai_win, bai_winv, bai_cnt, bai_start, bai_cid, bai_chunks;   // the index (bwamem_hip_batch_index_bam)
 };
 
 static const int LOG_TAB_N = 1 << 20;
@@ -1373,7 +1381,7 @@ static bool align_batch_pe(bwaidx_s* ix, const MemOpt& opt, const MemPestat* pes
 static void release_tile_outputs(bwamem_batch_s* b)
 {
     for (TileOut& t : b->tiles) { if (t.d && t.owned) (void)hipFree(t.d); if (t.d_off) (void)hipFree(t.d_off); }
-    b->tiles.clear(); b->result_bytes = 0; b->aligned = false; b->bam_bytes = 0; b->bgzf.bytes = 0;
+    b->tiles.clear(); b->result_bytes = 0; b->aligned = false; b->bam_bytes = 0; b->bgzf.bytes = 0; b->bam_encoded = b->bam_sorted = false;
 }
 
 // Tiles are independent, and every kernel of a tile ends in a tail of a few long-running reads; several tiles are
@@ -1751,12 +1759,12 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
     HIP_OK(hipSetDevice(ix->device));
     Workspace& ws = ix->ws;
     if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
-    b->bam_bytes = 0; b->bgzf.bytes = 0;
+    b->bam_bytes = 0; b->bgzf.bytes = 0; b->bam_encoded = b->bam_sorted = false;
     if (!b->keep_offsets) { fprintf(stderr, "[bwamem_hip] encode_bam: the batch was aligned without bwamem_hip_batch_keep_offsets\n"); return false; }
     if (!b->aligned) { fprintf(stderr, "[bwamem_hip] encode_bam: the batch holds no finished alignment\n"); return false; }
     if ((names == nullptr) != (name_off == nullptr)) { fprintf(stderr, "[bwamem_hip] encode_bam: names and their offsets go together\n"); return false; }
     const size_t n = b->n_reads;
-    if (n == 0) return true;
+    if (n == 0) { b->bam_encoded = true; return true; }
     if (n >= 0x7fffffffu) { fprintf(stderr, "[bwamem_hip] encode_bam: too many reads\n"); return false; }
     if (names) {
         if (name_off[0] < 0) { fprintf(stderr, "[bwamem_hip] encode_bam: negative name offset\n"); return false; }
@@ -1793,14 +1801,14 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
     HIP_OK(hipStreamSynchronize(ws.stream));
     if (err & BAM_ERR_CIGAR_OPS) { fprintf(stderr, "[bwamem_hip] encode_bam: a record has more than %d CIGAR operations (not representable without the CG tag)\n", BAM_MAX_CIGAR_OPS); return false; }
     if (err || total < 0) { fprintf(stderr, "[bwamem_hip] encode_bam: the resident response does not parse (flags %d)\n", err); return false; }
-    if (total == 0) return true;
+    if (total == 0) { b->bam_encoded = true; return true; }
     if (!b->bam.ensure((size_t)total)) return false;
     for (BamTile& t : tiles) { t.out = b->bam.as<uint8_t>(); launch_bam_emit(ws.stream, t); }
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(&err, b->bam_err.p, 4, hipMemcpyDeviceToHost, ws.stream));
     HIP_OK(hipStreamSynchronize(ws.stream));
     if (err) { fprintf(stderr, "[bwamem_hip] encode_bam: internal error while writing the records (flags %d)\n", err); return false; }
-    b->bam_bytes = (size_t)total;
+    b->bam_bytes = (size_t)total; b->bam_encoded = true;
     return true;
 }
 
@@ -1906,6 +1914,225 @@ void* bwamem_hip_bgzf_compress_device(bwaidx_t* idx, const void* src, size_t n, 
         if (!res) return nullptr;
         if (z.bytes && hipMemcpy(res, z.out.p, z.bytes, hipMemcpyDeviceToHost) != hipSuccess) { free(res); return nullptr; }
         if (pBytes) *pBytes = z.bytes;
+        return res;
+    });
+}
+
+// ---- coordinate-sorted records and their index (bam_sort.h; kernels next to the BAM kernels)
+static bool sort_ensure(SortBufs& s, int64_t n)
+{
+    const size_t nh = (size_t)SORT_RADIX * (size_t)sort_n_tiles(n);
+    return s.keys[0].ensure((size_t)n * 8) && s.keys[1].ensure((size_t)n * 8) && s.idx[0].ensure((size_t)n * 4) && s.idx[1].ensure((size_t)n * 4)
+        && s.hist.ensure(nh * 4) && s.hist_off.ensure((nh + 1) * 8) && s.scan_tmp.ensure(scan_tmp_bytes((int64_t)nh + 1)) && s.bits.ensure(SORT_BITS_N * 4);
+}
+// The passes over the bytes named by `live` of the n keys in s.keys[0] (sort_ensure'd), the indices starting as the identity:
+// *side = the side of s that holds the sorted keys and the permutation.  No host wait.
+static bool sort_pairs(Workspace& ws, SortBufs& s, int64_t n, uint32_t live, int* side)
+{
+    if (!(live & 0xff)) live = 1;                                      // nothing varies: one pass still writes the identity
+    int cur = 0;
+    bool first = true;
+    for (int byte = 0; byte < 8; ++byte) {
+        if (!(live >> byte & 1)) continue;
+        TIMED(ws, K_OTHER, launch_sort_hist(ws.stream, s.keys[cur].as<uint64_t>(), n, byte, s.hist.as<int32_t>()));
+        launch_scan(ws.stream, s.hist.as<int32_t>(), s.hist_off.as<int64_t>(), (int)(SORT_RADIX * sort_n_tiles(n)), s.scan_tmp.as<int64_t>());
+        TIMED(ws, K_OTHER, launch_sort_scatter(ws.stream, s.keys[cur].as<uint64_t>(), first ? nullptr : s.idx[cur].as<uint32_t>(), n, byte, s.hist_off.as<int64_t>(),
+                                               s.keys[cur ^ 1].as<uint64_t>(), s.idx[cur ^ 1].as<uint32_t>()));
+        cur ^= 1; first = false;
+    }
+    *side = cur;
+    return true;
+}
+
+// The device of b->idx is current and its lock held.  Two host waits: the record count (with the OR / AND of the keys) and the
+// total size.  The records are left as they were unless everything succeeded.
+static bool sort_bam(bwamem_batch_s* b)
+{
+    bwaidx_s* ix = b->idx;
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    if (!b->bam_encoded) { fprintf(stderr, "[bwamem_hip] sort_bam: the batch holds no encoded records\n"); return false; }
+    if (b->bam_sorted) return true;
+    b->bgzf.bytes = 0;
+    const size_t n = b->n_reads;
+    if (n == 0 || b->bam_bytes == 0) { b->bam_n_rec = 0; b->bam_sorted = true; return true; }
+    if (!(b->rec_cnt.ensure(n * 4) && b->rec_first.ensure((n + 1) * 8) && b->rec_scan_tmp.ensure(scan_tmp_bytes((int64_t)n + 1)) && b->srt.bits.ensure(SORT_BITS_N * 4)
+          && b->bam_err.ensure(64))) return false;
+    HIP_OK(hipMemsetAsync(b->srt.bits.p, 0, SORT_BITS_N * 4, ws.stream));
+    HIP_OK(hipMemsetAsync(b->bam_err.p, 0, 64, ws.stream));
+    TIMED(ws, K_OTHER, launch_bamrec_count(ws.stream, b->bam.as<uint8_t>(), b->bam_off.as<int64_t>(), (int)n, b->rec_cnt.as<int32_t>(), b->srt.bits.as<int32_t>(), b->bam_err.as<int32_t>()));
+    launch_scan(ws.stream, b->rec_cnt.as<int32_t>(), b->rec_first.as<int64_t>(), (int)n, b->rec_scan_tmp.as<int64_t>());
+    HIP_OK(hipGetLastError());
+    int64_t n_rec = 0; int32_t err = 0, bits[SORT_BITS_N];
+    HIP_OK(hipMemcpyAsync(&n_rec, b->rec_first.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(bits, b->srt.bits.p, sizeof bits, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(&err, b->bam_err.p, 4, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 1: the record count
+    if (err || n_rec <= 0) { fprintf(stderr, "[bwamem_hip] sort_bam: the encoded records do not chain (flags %d)\n", err); return false; }
+    if (n_rec >= 0x7fffffff) { fprintf(stderr, "[bwamem_hip] sort_bam: too many records\n"); return false; }
+    const size_t m = (size_t)n_rec;
+    if (!(sort_ensure(b->srt, n_rec) && b->rec_src.ensure(m * 8) && b->rec_size.ensure(m * 4) && b->rec_psize.ensure(m * 4) && b->rec_dst.ensure((m + 1) * 8)
+          && b->rec_scan_tmp.ensure(scan_tmp_bytes(n_rec + 1)) && b->bam2.ensure(b->bam_bytes))) return false;
+    TIMED(ws, K_OTHER, launch_bamrec_keys(ws.stream, b->bam.as<uint8_t>(), b->bam_off.as<int64_t>(), (int)n, b->rec_first.as<int64_t>(), b->srt.keys[0].as<uint64_t>(),
+                                          b->rec_src.as<int64_t>(), b->rec_size.as<int32_t>()));
+    int side = 0;
+    if (!sort_pairs(ws, b->srt, n_rec, sort_live_bytes(bits), &side)) return false;
+    TIMED(ws, K_OTHER, launch_bamrec_sizes(ws.stream, b->srt.idx[side].as<uint32_t>(), b->rec_size.as<int32_t>(), (int)n_rec, b->rec_psize.as<int32_t>()));
+    launch_scan(ws.stream, b->rec_psize.as<int32_t>(), b->rec_dst.as<int64_t>(), (int)n_rec, b->rec_scan_tmp.as<int64_t>());
+    HIP_OK(hipGetLastError());
+    int64_t total = 0;
+    HIP_OK(hipMemcpyAsync(&total, b->rec_dst.as<int64_t>() + m, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 2: the total size
+    if (total != (int64_t)b->bam_bytes) { fprintf(stderr, "[bwamem_hip] sort_bam: internal error: the sorted sizes do not add up\n"); return false; }
+    TIMED(ws, K_OTHER, launch_bamrec_gather(ws.stream, b->bam.as<uint8_t>(), b->rec_src.as<int64_t>(), b->srt.idx[side].as<uint32_t>(), b->rec_dst.as<int64_t>(), (int)n_rec, total,
+                                            b->bam2.as<uint8_t>()));
+    std::swap(b->bam, b->bam2);                                        // (later work is ordered behind the gather: the same stream, or the null stream)
+    b->bam_n_rec = m; b->bam_sorted = true;
+    return true;
+}
+
+int bwamem_hip_batch_sort_bam(bwamem_batch_t* b)
+{
+    return guarded("bwamem_hip_batch_sort_bam", -1, [&]() -> int {
+        if (!b || !b->idx) return -1;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+        const bool ok = sort_bam(b);
+        timed_collect(b->idx->ws);
+        return ok ? 0 : -1;
+    });
+}
+
+int bwamem_hip_sort_pairs_device(bwaidx_t* idx, const uint64_t* keys, size_t n, uint32_t* perm)
+{
+    return guarded("bwamem_hip_sort_pairs_device", -1, [&]() -> int {
+        if (!idx || (n && (!keys || !perm)) || n >= 0x7fffffffu) return -1;
+        if (n == 0) return 0;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (hipSetDevice(idx->device) != hipSuccess) return -1;
+        auto run = [&]() -> bool {
+            Workspace& ws = idx->ws;
+            if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+            SortBufs s;
+            if (!sort_ensure(s, (int64_t)n)) return false;
+            HIP_OK(hipMemcpyAsync(s.keys[0].p, keys, n * 8, hipMemcpyHostToDevice, ws.stream));
+            HIP_OK(hipMemsetAsync(s.bits.p, 0, SORT_BITS_N * 4, ws.stream));
+            TIMED(ws, K_OTHER, launch_sort_bits(ws.stream, s.keys[0].as<uint64_t>(), (int64_t)n, s.bits.as<int32_t>()));
+            int32_t bits[SORT_BITS_N];
+            HIP_OK(hipMemcpyAsync(bits, s.bits.p, sizeof bits, hipMemcpyDeviceToHost, ws.stream));
+            HIP_OK(hipStreamSynchronize(ws.stream));
+            int side = 0;
+            if (!sort_pairs(ws, s, (int64_t)n, sort_live_bytes(bits), &side)) return false;
+            HIP_OK(hipMemcpyAsync(perm, s.idx[side].p, n * 4, hipMemcpyDeviceToHost, ws.stream));
+            HIP_OK(hipStreamSynchronize(ws.stream));
+            timed_collect(ws);
+            return true;
+        };
+        return run() ? 0 : -1;
+    });
+}
+
+static void bai_put(std::string& o, const void* p, size_t n) { o.append((const char*)p, n); }      // (the library is little-endian throughout)
+
+static bool index_bam(bwamem_batch_s* b, int64_t coffset0, std::string& o)
+{
+    bwaidx_s* ix = b->idx;
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    if (!b->bam_sorted) { fprintf(stderr, "[bwamem_hip] index_bam: the records are not sorted (bwamem_hip_batch_sort_bam)\n"); return false; }
+    if (coffset0 < 0) { fprintf(stderr, "[bwamem_hip] index_bam: negative offset\n"); return false; }
+    const std::vector<ContigInfo>& contigs = ix->h.contigs;
+    const int32_t n_ref = (int32_t)contigs.size();
+    const size_t n_rec = b->bam_n_rec;
+    std::vector<int32_t> win_base((size_t)n_ref + 1, 0);
+    std::vector<BaiChunk> chunks;
+    std::vector<uint64_t> winv;
+    int32_t n_no_coor = 0;
+    if (n_rec > 0) {
+        if (b->bgzf.bytes == 0) { fprintf(stderr, "[bwamem_hip] index_bam: there are no members (bwamem_hip_batch_compress_bam after the sort)\n"); return false; }
+        if (n_rec >= 0x7fffffffu) { fprintf(stderr, "[bwamem_hip] index_bam: more than 2^31 - 1 records\n"); return false; }
+        int64_t n_win = 0;
+        for (int32_t i = 0; i < n_ref; ++i) { n_win += bai_n_windows((int64_t)contigs[i].len); if (n_win >= 0x7fffffff) { fprintf(stderr, "[bwamem_hip] index_bam: too many windows\n"); return false; } win_base[i + 1] = (int32_t)n_win; }
+        if (!(sort_ensure(b->srt, (int64_t)n_rec) && b->bai_win_base.ensure(((size_t)n_ref + 1) * 4) && b->bai_win.ensure((size_t)n_win * 4 + 4) && b->bai_winv.ensure((size_t)n_win * 8 + 8)
+              && b->bai_cnt.ensure(64) && b->bai_start.ensure(n_rec * 4) && b->bai_cid.ensure((n_rec + 1) * 8) && b->rec_scan_tmp.ensure(scan_tmp_bytes((int64_t)n_rec + 1)))) return false;
+        HIP_OK(hipMemcpyAsync(b->bai_win_base.p, win_base.data(), ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice, ws.stream));
+        HIP_OK(hipMemsetAsync(b->bai_win.p, 0xff, (size_t)n_win * 4 + 4, ws.stream));
+        HIP_OK(hipMemsetAsync(b->bai_cnt.p, 0, 64, ws.stream));
+        HIP_OK(hipMemsetAsync(b->srt.bits.p, 0, SORT_BITS_N * 4, ws.stream));
+        BaiView v; memset(&v, 0, sizeof v);
+        v.bam = b->bam.as<uint8_t>(); v.rec_off = b->rec_dst.as<int64_t>(); v.n_rec = (int32_t)n_rec; v.n_ref = n_ref;
+        v.win_base = b->bai_win_base.as<int32_t>(); v.win = b->bai_win.as<int32_t>(); v.keys = b->srt.keys[0].as<uint64_t>();
+        v.n_no_coor = b->bai_cnt.as<int32_t>(); v.err = b->bai_cnt.as<int32_t>() + 1;
+        TIMED(ws, K_OTHER, launch_bai_records(ws.stream, v));
+        TIMED(ws, K_OTHER, launch_sort_bits(ws.stream, v.keys, (int64_t)n_rec, b->srt.bits.as<int32_t>()));
+        int32_t bits[SORT_BITS_N], cnt[2];
+        HIP_OK(hipMemcpyAsync(bits, b->srt.bits.p, sizeof bits, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipMemcpyAsync(cnt, b->bai_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipStreamSynchronize(ws.stream));
+        if (cnt[1] & BAMSORT_ERR_END) { fprintf(stderr, "[bwamem_hip] index_bam: a record ends beyond 2^29 (not representable in a BAI index)\n"); return false; }
+        if (cnt[1]) { fprintf(stderr, "[bwamem_hip] index_bam: internal error: the sorted records do not parse (flags %d)\n", cnt[1]); return false; }
+        n_no_coor = cnt[0];
+        int side = 0;
+        if (!sort_pairs(ws, b->srt, (int64_t)n_rec, sort_live_bytes(bits), &side)) return false;
+        const uint64_t* k2 = b->srt.keys[side].as<uint64_t>(); const uint32_t* i2 = b->srt.idx[side].as<uint32_t>();
+        TIMED(ws, K_OTHER, launch_bai_mark(ws.stream, k2, i2, (int)n_rec, b->bai_start.as<int32_t>()));
+        launch_scan(ws.stream, b->bai_start.as<int32_t>(), b->bai_cid.as<int64_t>(), (int)n_rec, b->rec_scan_tmp.as<int64_t>());
+        HIP_OK(hipGetLastError());
+        int64_t n_chunks = 0;
+        HIP_OK(hipMemcpyAsync(&n_chunks, b->bai_cid.as<int64_t>() + n_rec, 8, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipStreamSynchronize(ws.stream));
+        if (n_chunks <= 0 || n_chunks > (int64_t)n_rec) { fprintf(stderr, "[bwamem_hip] index_bam: internal error: chunk count\n"); return false; }
+        if (!b->bai_chunks.ensure((size_t)n_chunks * sizeof(BaiChunk))) return false;
+        TIMED(ws, K_OTHER, launch_bai_chunks(ws.stream, k2, i2, (int)n_rec, b->bai_start.as<int32_t>(), b->bai_cid.as<int64_t>(), b->rec_dst.as<int64_t>(), b->bgzf.off.as<int64_t>(), coffset0,
+                                             b->bai_chunks.as<BaiChunk>()));
+        TIMED(ws, K_OTHER, launch_bai_windows(ws.stream, b->bai_win.as<int32_t>(), (int)n_win, (int)n_rec, b->rec_dst.as<int64_t>(), b->bgzf.off.as<int64_t>(), coffset0, b->bai_winv.as<uint64_t>()));
+        chunks.resize((size_t)n_chunks); winv.resize((size_t)n_win);
+        HIP_OK(hipMemcpyAsync(chunks.data(), b->bai_chunks.p, (size_t)n_chunks * sizeof(BaiChunk), hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipMemcpyAsync(winv.data(), b->bai_winv.p, (size_t)n_win * 8, hipMemcpyDeviceToHost, ws.stream));
+        HIP_OK(hipStreamSynchronize(ws.stream));
+        timed_collect(ws);
+    }
+    // the bytes: the chunks arrive ordered by (refID, bin) and, within a bin, in file order
+    o.assign("BAI\1", 4);
+    bai_put(o, &n_ref, 4);
+    size_t c = 0;
+    for (int32_t ref = 0; ref < n_ref; ++ref) {
+        const size_t c0 = c;
+        int32_t n_bin = 0;
+        for (; c < chunks.size() && chunks[c].key >> 32 == (uint64_t)(uint32_t)ref; ++c) if (c == c0 || chunks[c].key != chunks[c - 1].key) ++n_bin;
+        bai_put(o, &n_bin, 4);
+        for (size_t k = c0; k < c;) {
+            size_t e = k;
+            while (e < c && chunks[e].key == chunks[k].key) ++e;
+            const uint32_t bin = (uint32_t)chunks[k].key; const int32_t n_chunk = (int32_t)(e - k);
+            bai_put(o, &bin, 4); bai_put(o, &n_chunk, 4);
+            for (; k < e; ++k) { bai_put(o, &chunks[k].beg, 8); bai_put(o, &chunks[k].end, 8); }
+        }
+        int32_t n_intv = 0;
+        const int32_t w0 = n_rec ? win_base[ref] : 0, w1 = n_rec ? win_base[ref + 1] : 0;
+        for (int32_t w = w0; w < w1; ++w) if (winv[w] != SORT_KEY_LAST) n_intv = w - w0 + 1;
+        bai_put(o, &n_intv, 4);
+        uint64_t prev = 0;
+        for (int32_t w = w0; w < w0 + n_intv; ++w) { if (winv[w] != SORT_KEY_LAST) prev = winv[w]; bai_put(o, &prev, 8); }
+    }
+    const uint64_t nnc = (uint64_t)(uint32_t)n_no_coor;
+    bai_put(o, &nnc, 8);
+    return true;
+}
+
+void* bwamem_hip_batch_index_bam(bwamem_batch_t* b, int64_t coffset0, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    return guarded("bwamem_hip_batch_index_bam", (void*)0, [&]() -> void* {
+        if (!b || !b->idx) return nullptr;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        if (hipSetDevice(b->idx->device) != hipSuccess) return nullptr;
+        std::string o;
+        if (!index_bam(b, coffset0, o)) return nullptr;
+        void* res = malloc(o.size() ? o.size() : 1);
+        if (!res) return nullptr;
+        memcpy(res, o.data(), o.size());
+        if (pBytes) *pBytes = o.size();
         return res;
     });
 }

@@ -412,4 +412,76 @@ int bwamem_hip_align_to_bam_device(bwaidx_t* idx, const mem_opt_t* opt, const me
     } catch (...) { return -1; }
 }
 
+// bwamem_hip_bam_header with the @HD line of a coordinate-sorted file
+void* bwamem_hip_bam_header_sorted(bwaidx_t* idx, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    try {
+        size_t n = 0;
+        Freed hdr(bwamem_hip_bam_header(idx, &n));
+        if (!hdr.p || n < 8) return 0;
+        const uint8_t* h = (const uint8_t*)hdr.p;
+        const size_t l_text = (size_t)h[4] | (size_t)h[5] << 8 | (size_t)h[6] << 16 | (size_t)h[7] << 24;
+        const void* eol = l_text <= n - 8 ? memchr(h + 8, '\n', l_text) : 0;
+        if (!eol) return 0;
+        std::string text("@HD\tVN:1.6\tSO:coordinate");
+        text.append((const char*)eol, (const char*)h + 8 + l_text);
+        std::string o("BAM\1", 4);
+        uint8_t b[4]; le32(b, (uint32_t)text.size());
+        o.append((const char*)b, 4); o += text; o.append((const char*)h + 8 + l_text, n - 8 - l_text);
+        void* r = malloc(o.size());
+        if (!r) return 0;
+        memcpy(r, o.data(), o.size());
+        if (pBytes) *pBytes = o.size();
+        return r;
+    } catch (...) { return 0; }
+}
+
+// bwamem_hip_align_to_bam_device with the records coordinate-sorted on the device, and the BAI index into fd_bai when asked for
+int bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
+                                   int fd, int fd_bai, int write_header)
+{
+    try {
+        if (!idx || !opt || !pSeq || nBytes < 4 || fd < 0) return -1;
+        if (fd_bai >= 0 && !write_header) { fprintf(stderr, "[bwamem_hip] align_to_sorted_bam: an index needs the header in the same file\n"); return -1; }
+        uint32_t n_reads; memcpy(&n_reads, pSeq, 4);
+        int32_t flag; memcpy(&flag, (const char*)opt + 60, 4);                  // mem_opt_t.flag (BwaMemAligner.java:75)
+        const int paired = (flag & 0x2) != 0;
+        std::string blob; std::vector<int64_t> name_off;
+        if (readNames) {
+            name_off.reserve((size_t)n_reads + 1);
+            for (uint32_t i = 0; i < n_reads; ++i) { name_off.push_back((int64_t)blob.size()); if (readNames[i]) blob += readNames[i]; }
+            name_off.push_back((int64_t)blob.size());
+        }
+        BatchOwner bo{ bwamem_hip_batch_upload(idx, pSeq, nBytes) };
+        if (!bo.b) return -1;
+        if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
+        if (bwamem_hip_batch_encode_bam(bo.b, paired, readNames ? blob.data() : nullptr, readNames ? name_off.data() : nullptr) != 0) return -1;
+        if (bwamem_hip_batch_sort_bam(bo.b) != 0) return -1;
+        // everything is made before the first byte is written
+        size_t nh = 0, nzh = 0, nz = 0, nb = 0;
+        Freed zh, z, bai;
+        if (write_header) {
+            Freed hdr(bwamem_hip_bam_header_sorted(idx, &nh));
+            if (!hdr.p) return -1;
+            zh.p = bwamem_hip_bgzf_compress_device(idx, hdr.p, nh, 0, &nzh);
+            if (!zh.p) return -1;
+        }
+        if (bwamem_hip_batch_bam_bytes(bo.b) != 0) {
+            if (bwamem_hip_batch_compress_bam(bo.b, 1) != 0) return -1;
+            nz = bwamem_hip_batch_bgzf_bytes(bo.b);
+            z.p = malloc(nz ? nz : 1);
+            if (!z.p || bwamem_hip_batch_bgzf_download(bo.b, z.p) != 0) return -1;
+        }
+        if (fd_bai >= 0) {
+            bai.p = bwamem_hip_batch_index_bam(bo.b, (int64_t)nzh, &nb);
+            if (!bai.p) return -1;
+        }
+        if (write_header && !write_all(fd, (const uint8_t*)zh.p, nzh)) return -1;
+        if (z.p ? !write_all(fd, (const uint8_t*)z.p, nz) : !write_all(fd, BGZF_EOF, sizeof BGZF_EOF)) return -1;      // no record: the EOF block alone
+        if (fd_bai >= 0 && !write_all(fd_bai, (const uint8_t*)bai.p, nb)) return -1;
+        return 0;
+    } catch (...) { return -1; }
+}
+
 }  // extern "C"

@@ -157,6 +157,32 @@ void*  bwamem_hip_bgzf_compress_device(bwaidx_t* idx, const void* src, size_t n,
 int    bwamem_hip_align_to_bam_device(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes,
                                       const char* const* readNames, int fd, int write_header);
 
+/* Coordinate-sorted BAM and its BAI index, sorted and indexed on the device (csrc/bam_sort.h; additive): while the records sit in
+ * HBM next to the compressor they are sorted by (refID, pos) -- a stable radix sort of 8-byte keys and one gather -- and the index
+ * is made where both the records' places and the members' offsets are known.  Sorted means sorted within the call (one
+ * jnibwa_createAlignments request, under 2 GiB of records); merging the sorted runs of several calls is the caller's business.
+ *   _sort_bam       after _encode_bam: the records ordered by (uint32)refID, then (uint32)pos, both read from the records -- unplaced
+ *                   reads last, a placed unmapped mate at its mate's place, ties in response order.  From here _bam_bytes,
+ *                   _bam_download and _compress_bam see the sorted records.  Non-zero, and the records as they were, without encoded
+ *                   records; 0 and nothing done when they are sorted already.  Discards BGZF members; _encode_bam and a new
+ *                   alignment of the batch discard the sorted state.
+ *   _index_bam      after _sort_bam and then _compress_bam: the bytes of the .bai file (jnibwa_free) for a BAM file in which
+ *                   coffset0 bytes (the compressed header) precede the first member of the records; the rules are at the top of
+ *                   csrc/bam_sort.h.  NULL with a message when the batch is not sorted, has no members, or a record ends beyond
+ *                   2^29.  A sorted batch without records gives the empty index.
+ *   bwamem_hip_bam_header_sorted     bwamem_hip_bam_header with the first line "@HD\tVN:1.6\tSO:coordinate"
+ *   bwamem_hip_align_to_sorted_bam   bwamem_hip_align_to_bam_device with _sort_bam between encode and compress and the sorted
+ *                   header; fd_bai >= 0: the index is written there as well, which needs write_header (otherwise an error, and
+ *                   nothing is written)
+ *   bwamem_hip_sort_pairs_device     tooling: host keys in, the stable sorting permutation out (perm[i] = the index of the i-th
+ *                   smallest key, ties in input order), through the same kernels; idx selects the device.  0 = ok. */
+int    bwamem_hip_batch_sort_bam(bwamem_batch_t* b);
+void*  bwamem_hip_batch_index_bam(bwamem_batch_t* b, int64_t coffset0, size_t* pBytes);   /* jnibwa_free */
+void*  bwamem_hip_bam_header_sorted(bwaidx_t* idx, size_t* pBytes);                        /* jnibwa_free */
+int    bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes,
+                                      const char* const* readNames, int fd, int fd_bai, int write_header);
+int    bwamem_hip_sort_pairs_device(bwaidx_t* idx, const uint64_t* keys, size_t n, uint32_t* perm);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
