@@ -43,6 +43,31 @@ _lib.bwamem_hip_align_to_bam_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p
                                                 ctypes.c_int, ctypes.c_int]
 _lib.bwamem_hip_align_to_sorted_bam.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int]
+_vp, _sz, _i64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64
+_lib.bwamem_hip_batch_upload.restype = _vp; _lib.bwamem_hip_batch_upload.argtypes = [_vp, ctypes.c_char_p, _sz]
+_lib.bwamem_hip_batch_free.restype = None; _lib.bwamem_hip_batch_free.argtypes = [_vp]
+_lib.bwamem_hip_batch_keep_offsets.argtypes = [_vp, ctypes.c_int]
+_lib.bwamem_hip_batch_align.argtypes = [_vp, _vp, _vp, _vp, _i64]
+_lib.bwamem_hip_batch_set_qualities.argtypes = [_vp, ctypes.c_char_p, _sz]
+_lib.bwamem_hip_batch_set_read_group.argtypes = [_vp, ctypes.c_char_p]
+_lib.bwamem_hip_batch_encode_bam.argtypes = [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_i64)]
+_lib.bwamem_hip_batch_sort_bam.argtypes = [_vp]
+_lib.bwamem_hip_batch_bam_bytes.restype = _sz; _lib.bwamem_hip_batch_bam_bytes.argtypes = [_vp]
+_lib.bwamem_hip_batch_compress_bam.argtypes = [_vp, ctypes.c_int]
+_lib.bwamem_hip_batch_bgzf_bytes.restype = _sz; _lib.bwamem_hip_batch_bgzf_bytes.argtypes = [_vp]
+_lib.bwamem_hip_batch_bgzf_download.argtypes = [_vp, _vp]
+_lib.bwamem_hip_batch_index_bam.restype = _vp; _lib.bwamem_hip_batch_index_bam.argtypes = [_vp, _i64, ctypes.POINTER(_sz)]
+_lib.bwamem_hip_bam_header_rg.restype = _vp; _lib.bwamem_hip_bam_header_rg.argtypes = [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(_sz)]
+_lib.bwamem_hip_bgzf_compress_device.restype = _vp; _lib.bwamem_hip_bgzf_compress_device.argtypes = [_vp, _vp, _sz, ctypes.c_int, ctypes.POINTER(_sz)]
+_lib.bwamem_hip_align_fastq_to_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.c_char_p, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int]
+_BGZF_EOF = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0])
+
+
+def _taken(p, n):
+    out = ctypes.string_at(p, n)
+    _lib.jnibwa_free(p)
+    return out
 
 
 class CouldNotReadImageException(RuntimeError):
@@ -326,14 +351,17 @@ class BwaMemAligner:
         finally:
             self.index.deRefIndex()
 
-    def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False, sort=False, index_path=None):
+    def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False, sort=False, index_path=None, quals=None,
+                       read_group=None):
         """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
         `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
         "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred).
         device=True: the BGZF blocks are compressed on the device as well (DEFLATE with dynamic Huffman codes; `level` is ignored
         and libz is not needed).
         sort=True (implies device=True): the records are coordinate-sorted on the device within this call and the header says
-        SO:coordinate; index_path: the BAI index of that file is written there as well (needs sort=True)."""
+        SO:coordinate; index_path: the BAI index of that file is written there as well (needs sort=True).
+        quals: one Phred+33 string per sequence, each as long as its sequence: the records carry them as QUAL.  read_group: an
+        "@RG\\tID:..." header line: it goes into the header, and every record carries RG:Z:<ID>.  Either implies device=True."""
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
         opts = self._getOpts()
@@ -341,6 +369,8 @@ class BwaMemAligner:
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
         if names is not None and len(names) != len(seqs):
             raise ValueError("%d names for %d sequences" % (len(names), len(seqs)))
+        if quals is not None or read_group is not None:
+            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group)
         buf = struct.pack("=i", len(seqs)) + b"".join(s + b"\0" for s in seqs)
         arr = None
         if names is not None:
@@ -368,6 +398,105 @@ class BwaMemAligner:
             self.index.deRefIndex()
         if rc != 0:
             raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s" % (self.index.indexImageFile, path))
+
+    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group):
+        """alignSeqsToBam through the batch calls, which take qualities and a read group; nothing is written unless all of it succeeds"""
+        if quals is not None:
+            quals = [q.encode() if isinstance(q, str) else bytes(q) for q in quals]
+            if len(quals) != len(seqs) or any(len(q) != len(s) for q, s in zip(quals, seqs)):
+                raise ValueError("one quality string per sequence, each as long as its sequence")
+        rg = None if read_group is None else read_group.encode() if isinstance(read_group, str) else bytes(read_group)
+        buf = struct.pack("=i", len(seqs)) + b"".join(s + b"\0" for s in seqs)
+        blob, off = None, None
+        if names is not None:
+            enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+            ends = [0]
+            for n in enc:
+                ends.append(ends[-1] + len(n))
+            blob, off = b"".join(enc), (ctypes.c_int64 * len(ends))(*ends)
+        pes = self.pairEndStats
+        pb = ctypes.create_string_buffer(pes._pack(), 128) if pes is not None else None
+        paired = 1 if self.getFlagOption() & self.MEM_F_PE else 0
+        fail = RuntimeError("Unable to write alignments of bwa-mem index %s to %s" % (self.index.indexImageFile, path))
+        idx = self.index.refIndex()
+        b = None
+        try:
+            b = _lib.bwamem_hip_batch_upload(idx, buf, len(buf))
+            if not b:
+                raise fail
+            if quals is not None:
+                qb = b"".join(q + b"\0" for q in quals)
+                if _lib.bwamem_hip_batch_set_qualities(b, qb, len(qb)) != 0:
+                    raise ValueError("the qualities were refused: every byte must be in 33..126")
+            if rg is not None and _lib.bwamem_hip_batch_set_read_group(b, rg) != 0:
+                raise ValueError("the read group was refused: one '@RG\\t' line with an ID: field of 1..254 bytes")
+            if _lib.bwamem_hip_batch_keep_offsets(b, 1) != 0 or _lib.bwamem_hip_batch_align(idx, self._getOpts(), pb, b, 0) != 0:
+                raise fail
+            if _lib.bwamem_hip_batch_encode_bam(b, paired, blob, off) != 0 or (sort and _lib.bwamem_hip_batch_sort_bam(b) != 0):
+                raise fail
+            sz = ctypes.c_size_t()
+            p = _lib.bwamem_hip_bam_header_rg(idx, 1 if sort else 0, rg, ctypes.byref(sz))
+            if not p:
+                raise fail
+            hdr = _taken(p, sz.value)
+            p = _lib.bwamem_hip_bgzf_compress_device(idx, hdr, len(hdr), 0, ctypes.byref(sz))
+            if not p:
+                raise fail
+            zh, z, bai = _taken(p, sz.value), _BGZF_EOF, None
+            if _lib.bwamem_hip_batch_bam_bytes(b):
+                if _lib.bwamem_hip_batch_compress_bam(b, 1) != 0:
+                    raise fail
+                zb = ctypes.create_string_buffer(_lib.bwamem_hip_batch_bgzf_bytes(b))
+                if _lib.bwamem_hip_batch_bgzf_download(b, zb) != 0:
+                    raise fail
+                z = zb.raw
+            if index_path is not None:
+                p = _lib.bwamem_hip_batch_index_bam(b, len(zh), ctypes.byref(sz))
+                if not p:
+                    raise fail
+                bai = _taken(p, sz.value)
+        finally:
+            if b:
+                _lib.bwamem_hip_batch_free(b)
+            self.index.deRefIndex()
+        with open(path, "wb") as f:
+            f.write(zh + z)
+        if bai is not None:
+            with open(index_path, "wb") as f:
+                f.write(bai)
+
+    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None):
+        """Additive: FASTQ in, a BAM file out.  fastq1 / fastq2: FASTQ text (bytes), or the path of an uncompressed FASTQ file (str);
+        with fastq2 the two hold the first and second reads of the pairs, without it fastq1 holds single-end reads or -- after
+        alignPairs() -- interleaved pairs.  The text is taken apart on the device: the records carry the reads' names and base
+        qualities, and RG:Z:<ID> when read_group (an "@RG\\tID:..." header line) is given.  sort / index_path as alignSeqsToBam."""
+        if index_path is not None and not sort:
+            raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
+        opts = self._getOpts()
+
+        def text(x):
+            if x is None or isinstance(x, (bytes, bytearray)):
+                return None if x is None else bytes(x)
+            with open(x, "rb") as f:
+                return f.read()
+        t1, t2 = text(fastq1), text(fastq2)
+        rg = None if read_group is None else read_group.encode() if isinstance(read_group, str) else bytes(read_group)
+        pes = self.pairEndStats
+        pb = ctypes.create_string_buffer(pes._pack(), 128) if pes is not None else None
+        idx = self.index.refIndex()
+        try:
+            fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+            fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
+            try:
+                rc = _lib.bwamem_hip_align_fastq_to_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, rg, 1 if sort else 0, fd, fd_bai, 1)
+            finally:
+                os.close(fd)
+                if fd_bai >= 0:
+                    os.close(fd_bai)
+        finally:
+            self.index.deRefIndex()
+        if rc != 0:
+            raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s (malformed FASTQ, or a device error)" % (self.index.indexImageFile, path))
 
     def alignSeqs(self, sequences, func=lambda s: s):
         """BwaMemAligner.java:192-310: one list of BwaMemAlignment per input sequence"""

@@ -14,9 +14,12 @@
 //   SEQ              4-bit codes of "=ACMGRSVTWYHKDBN" from the request's ASCII (either case; any other byte is N), reverse-
 //                    complemented (A<->T, C<->G, the other codes stay, as the SAM writer's comp()) when flag 0x10 is set,
 //                    trimmed to the unclipped part on hard-clipped records
-//   QUAL             l_seq bytes of 0xFF (the request carries no qualities)
+//   QUAL             l_seq bytes of 0xFF when the batch carries no qualities (bwamem_hip_batch_set_qualities, or a batch made
+//                    from FASTQ text); else byte q is qual[i] - 33 with i the index bam_seq_code uses for SEQ base q: reversed
+//                    where SEQ is reverse-complemented, trimmed where SEQ is hard-clipped
 //   tags             NM, MD (if non-empty), AS, XS (if >= 0), XA (if non-empty); integers in the smallest type that holds
-//                    the value (C S I for non-negative ones, c s i for negative ones), strings as Z
+//                    the value (C S I for non-negative ones, c s i for negative ones), strings as Z.  With a read group
+//                    (bwamem_hip_batch_set_read_group) RG:Z:<ID> comes last on every record, unmapped ones included
 //   read names       the caller's (1..254 bytes each), else "r<index>" / "p<pair index>" with the index counted over the
 //                    whole logical call (read_id0 of the align call + the index within the batch)
 #pragma once
@@ -70,7 +73,9 @@ struct BamRec {
     // the name
     const uint8_t* name; int32_t l_name; uint64_t name_idx; uint8_t name_letter;     // name == null: name_letter + decimal name_idx
     // offsets of the sections within the BAM record (block_size at 0, the fixed fields up to 36)
-    int32_t o_cigar, o_seq, o_qual, o_nm, o_md, o_as, o_xs, o_xa, total;
+    int32_t o_cigar, o_seq, o_qual, o_nm, o_md, o_as, o_xs, o_xa, o_rg, total;
+    // the read group's ID (null: no RG tag); bam_parse leaves none, bam_name sets the tile's
+    const uint8_t* rg; int32_t l_rg;
 };
 
 // Parses the k-th record of a read (k counts from 0: later mapped records are hard-clipped) at p, of at most n_avail words; l_read =
@@ -78,6 +83,7 @@ struct BamRec {
 // -> 0, or BAM_ERR_* (R is then unusable).
 BAM_HD int bam_parse(const uint32_t* p, int64_t n_avail, int k, int32_t l_read, int32_t n_seqs, BamRec& R)
 {
+    R.rg = 0; R.l_rg = 0;
     if (n_avail < 1) return BAM_ERR_PARSE;
     const uint32_t fm = p[0];
     int64_t at = 1;
@@ -155,6 +161,7 @@ BAM_HD int32_t bam_layout(BamRec& R)
     R.o_as = (int32_t)o;    if (R.mapped) o += 3 + bam_int_width(R.as);
     R.o_xs = (int32_t)o;    if (R.mapped && R.xs >= 0) o += 3 + bam_int_width(R.xs);
     R.o_xa = (int32_t)o;    if (R.mapped && R.n_xa > 0) o += 3 + (int64_t)R.n_xa + 1;
+    R.o_rg = (int32_t)o;    if (R.rg) o += 3 + (int64_t)R.l_rg + 1;
     R.total = o > 0x7fffffff ? -1 : (int32_t)o;
     return R.total;
 }
@@ -176,8 +183,15 @@ BAM_HD int bam_seq_code(const BamRec& R, const uint8_t* raw, int32_t q)
     return R.flag & 0x10 ? bam_comp_code(bam_base_code(raw[R.l_read - 1 - i])) : bam_base_code(raw[i]);
 }
 
-// the byte at position i (0 <= i < R.total) of the BAM record
-BAM_HD uint8_t bam_byte(const BamRec& R, const uint8_t* raw, int32_t i)
+// byte q of QUAL; qual = the read's Phred+33 string, laid out like raw
+BAM_HD uint8_t bam_qual_byte(const BamRec& R, const uint8_t* qual, int32_t q)
+{
+    const int32_t i = R.seq_b + q;
+    return (uint8_t)(qual[R.flag & 0x10 ? R.l_read - 1 - i : i] - 33);
+}
+
+// the byte at position i (0 <= i < R.total) of the BAM record; qual = the read's qualities, or null (none: 0xFF)
+BAM_HD uint8_t bam_byte(const BamRec& R, const uint8_t* raw, int32_t i, const uint8_t* qual = 0)
 {
     if (i < 36) {
         uint32_t w;
@@ -213,12 +227,30 @@ BAM_HD uint8_t bam_byte(const BamRec& R, const uint8_t* raw, int32_t i)
         const int32_t q = 2 * (i - R.o_seq);
         return (uint8_t)(bam_seq_code(R, raw, q) << 4 | bam_seq_code(R, raw, q + 1));
     }
-    if (i < R.o_nm) return 0xff;
+    if (i < R.o_nm) return qual ? bam_qual_byte(R, qual, i - R.o_qual) : (uint8_t)0xff;
     if (i < R.o_md) return bam_int_tag_byte('N', 'M', R.nm, i - R.o_nm);
     if (i < R.o_as) return bam_str_tag_byte('M', 'D', R.md, R.n_md, i - R.o_md);
     if (i < R.o_xs) return bam_int_tag_byte('A', 'S', R.as, i - R.o_as);
     if (i < R.o_xa) return bam_int_tag_byte('X', 'S', R.xs, i - R.o_xs);
-    return bam_str_tag_byte('X', 'A', R.xa, R.n_xa, i - R.o_xa);
+    if (i < R.o_rg) return bam_str_tag_byte('X', 'A', R.xa, R.n_xa, i - R.o_xa);
+    return bam_str_tag_byte('R', 'G', R.rg, R.l_rg, i - R.o_rg);
+}
+
+// A read group's header line (bwamem_hip_batch_set_read_group): one line that begins with "@RG\t", has an ID: field of 1..254
+// bytes and holds no '\n', '\r' or NUL (the last by construction: the line is a C string).  -> the ID's place in the line and its
+// length, or 0 when the line is refused.
+BAM_HD int bam_rg_id(const char* line, const char** id)
+{
+    if (!line || line[0] != '@' || line[1] != 'R' || line[2] != 'G' || line[3] != '\t') return 0;
+    const char* found = 0; int l_found = 0;
+    for (const char* p = line + 3; *p; ) {                               // p at a tab: a field follows
+        const char* f = ++p;
+        while (*p && *p != '\t') { if (*p == '\n' || *p == '\r') return 0; ++p; }
+        if (!found && p - f >= 3 && f[0] == 'I' && f[1] == 'D' && f[2] == ':') { found = f + 3; l_found = (int)(p - f - 3); if (p - f - 3 > 254) return 0; }
+    }
+    if (!found || l_found < 1) return 0;
+    *id = found;
+    return l_found;
 }
 
 // What the size and emit kernels see of one tile of a batch (k_post.hip: launch_bam_size / launch_bam_emit).
@@ -232,6 +264,9 @@ struct BamTile {
     int32_t paired, n_seqs;
     const uint8_t* names;         // caller's names (device) and the offsets of this tile's, [n_reads + 1]; or both null
     const int64_t* name_off;
+    const uint8_t* qual;          // the batch's qualities (device), laid out like raw; or null
+    const uint8_t* rg;            // the read group's ID (device), l_rg bytes; or null
+    int32_t l_rg;
     int32_t* sizes;               // [n_reads] BAM bytes of each read's records (size kernel)
     const int64_t* out_off;       // [n_reads + 1] their places in out (after the scan)
     uint8_t* out;
@@ -243,4 +278,5 @@ BAM_HD void bam_name(const BamTile& t, int r, BamRec& R)
 {
     if (t.names) { R.name = t.names + t.name_off[r]; R.l_name = (int32_t)(t.name_off[r + 1] - t.name_off[r]); R.name_idx = 0; R.name_letter = 0; }
     else bam_default_name(R, t.paired, (uint64_t)(t.read_index0 + r));
+    R.rg = t.rg; R.l_rg = t.l_rg;
 }

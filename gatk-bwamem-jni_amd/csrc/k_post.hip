@@ -11,6 +11,7 @@
 #include "post_common.h"
 #include "bgzf_deflate.h"
 #include "bam_sort.h"
+#include "fastq_parse.h"
 
 // WAVE_PER_READ = false: one lane per read.  true (tiles of long reads): one wavefront per read -- sixty-four times the waves
 // in flight for this latency-bound stage -- with lane 0 doing the updates and the banded global alignments of region
@@ -161,8 +162,8 @@ __global__ void __launch_bounds__(64) k_bam_size(BamTile t)
 // step 3: G lanes per read (8, or the wavefront for tiles of long reads) write the read's records.  Every lane parses the record
 // (the same few words for all of them); the lanes then share out the aligned 32-bit words of the record's span in the output,
 // each assembled in a register from bam_byte and stored whole.  Only the up to three bytes before the first aligned word
-// and after the last are stored singly.
-template <int G>
+// and after the last are stored singly.  Q: the batch carries qualities (the instantiation without them has no load for QUAL).
+template <int G, bool Q>
 __global__ void __launch_bounds__(256) k_bam_emit(BamTile t)
 {
     const int r = blockIdx.x * (256 / G) + ((int)threadIdx.x / G), sub = (int)threadIdx.x % G;
@@ -174,6 +175,7 @@ __global__ void __launch_bounds__(256) k_bam_emit(BamTile t)
     const uint32_t* p = (const uint32_t*)(t.resp + lo);
     const int64_t n = (hi - lo) >> 2;
     const uint8_t* raw = t.raw + t.raw_off[r];
+    const uint8_t* qual = Q ? t.qual + t.raw_off[r] : nullptr;
     const int32_t l_read = (int32_t)(t.raw_off[r + 1] - t.raw_off[r] - 1);
     const int32_t n_aln = (int32_t)p[0];
     int64_t at = 1;
@@ -185,15 +187,134 @@ __global__ void __launch_bounds__(256) k_bam_emit(BamTile t)
         uint8_t* dst = t.out + o;
         const int32_t lead = (int32_t)((4 - (o & 3)) & 3), head = R.total < lead ? R.total : lead;
         const int32_t nw = (R.total - head) >> 2, tail = R.total - head - 4 * nw;
-        if (sub < head) dst[sub] = bam_byte(R, raw, sub);
+        if (sub < head) dst[sub] = bam_byte(R, raw, sub, qual);
         uint32_t* dw = (uint32_t*)(dst + head);
         for (int32_t w = sub; w < nw; w += G) {
             const int32_t i = head + 4 * w;
-            dw[w] = (uint32_t)bam_byte(R, raw, i) | (uint32_t)bam_byte(R, raw, i + 1) << 8 | (uint32_t)bam_byte(R, raw, i + 2) << 16 | (uint32_t)bam_byte(R, raw, i + 3) << 24;
+            dw[w] = (uint32_t)bam_byte(R, raw, i, qual) | (uint32_t)bam_byte(R, raw, i + 1, qual) << 8 | (uint32_t)bam_byte(R, raw, i + 2, qual) << 16 | (uint32_t)bam_byte(R, raw, i + 3, qual) << 24;
         }
-        if (sub < tail) dst[head + 4 * nw + sub] = bam_byte(R, raw, head + 4 * nw + sub);
+        if (sub < tail) dst[head + 4 * nw + sub] = bam_byte(R, raw, head + 4 * nw + sub, qual);
         o += R.total; at += R.words;
     }
+}
+
+// the qualities handed to bwamem_hip_batch_set_qualities against the reads, one lane per read: a NUL where the read's NUL is,
+// every other byte in 33..126.  err: FASTQ_NO_ERROR - the smallest offending read (0: none)
+__global__ void __launch_bounds__(64) k_qual_check(const uint8_t* raw, const uint8_t* qual, const int64_t* raw_off, int n_reads, int32_t* err)
+{
+    const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (r >= n_reads) return;
+    const int64_t lo = raw_off[r], hi = raw_off[r + 1] - 1;
+    bool bad = hi < lo || qual[hi] != 0;
+    for (int64_t i = lo; i < hi && !bad; ++i) bad = qual[i] < 33 || qual[i] > 126;
+    if (bad) atomicMax(err, FASTQ_NO_ERROR - r);
+}
+
+// the names of the two reads of every pair must be equal (paired calls on batches with names of their own), one lane per pair
+__global__ void __launch_bounds__(64) k_mate_names(const uint8_t* names, const int64_t* name_off, int n_pairs, int32_t* err)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n_pairs) return;
+    const int64_t a = name_off[2 * i], b = name_off[2 * i + 1], l = b - a;
+    bool bad = name_off[2 * i + 2] - b != l;
+    for (int64_t k = 0; k < l && !bad; ++k) bad = names[a + k] != names[b + k];
+    if (bad) atomicMax(err, FASTQ_NO_ERROR - 2 * i);
+}
+
+// ------------------------------------------------------------------ FASTQ text taken apart on the device (fastq_parse.h)
+// the newlines among the lane's FASTQ_LANE_BYTES positions from p0 (one 16-byte load where the text covers them all), as a bit per
+// position
+static __device__ inline uint32_t fastq_lane_newlines(const uint8_t* text, int64_t n, int64_t p0)
+{
+    uint32_t m = 0;
+    if (p0 + FASTQ_LANE_BYTES <= n) {
+        const uint4 v = *(const uint4*)(text + p0);
+        const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t b = fastq_newline_bits(w[k]);
+            m |= ((b >> 7 & 1) | (b >> 14 & 2) | (b >> 21 & 4) | (b >> 28 & 8)) << (4 * k);
+        }
+    } else
+        for (int k = 0; k < FASTQ_LANE_BYTES && p0 + k <= n; ++k) m |= (uint32_t)fastq_newline_at(text, n, p0 + k) << k;
+    return m;
+}
+
+// (a) the newlines of every chunk
+__global__ void __launch_bounds__(FASTQ_THREADS) k_fastq_count(const uint8_t* text, int64_t n, int32_t* counts)
+{
+    __shared__ int s_w[FASTQ_THREADS / 64];
+    const int tid = (int)threadIdx.x;
+    int c = __popc(fastq_lane_newlines(text, n, (int64_t)blockIdx.x * FASTQ_CHUNK + (int64_t)tid * FASTQ_LANE_BYTES));
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((tid & 63) == 0) s_w[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) { int tot = 0; for (int w = 0; w < FASTQ_THREADS / 64; ++w) tot += s_w[w]; counts[blockIdx.x] = tot; }
+}
+
+// (c) the start of every line: the number of a newline is its chunk's base plus a workgroup scan of the lanes' counts
+__global__ void __launch_bounds__(FASTQ_THREADS) k_fastq_starts(FastqText t)
+{
+    __shared__ int s_w[FASTQ_THREADS / 64];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * FASTQ_CHUNK + (int64_t)tid * FASTQ_LANE_BYTES;
+    uint32_t m = fastq_lane_newlines(t.text, t.n, p0);
+    const int c = __popc(m);
+    int incl = c;
+    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (lane >= o) incl += u; }
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    int pre = 0;
+    for (int w = 0; w < wv; ++w) pre += s_w[w];
+    int64_t j = t.chunk_base[blockIdx.x] + pre + incl - c + 1;       // the number of the lane's first newline
+    if (blockIdx.x == 0 && tid == 0 && t.n_lines >= 0) t.start[0] = 0;
+    for (; m; m &= m - 1, ++j)
+        if (j <= t.n_lines) t.start[j] = p0 + (__ffsll((long long)m) - 1) + 1;       // never outside the index
+}
+
+// (d) one lane per record checks its four lines and writes the lengths of its read; the smallest offending read into the error word
+__global__ void __launch_bounds__(64) k_fastq_records(FastqText t, FastqOut o)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= t.n_rec) return;
+    const int64_t read = (int64_t)t.stride * i + t.phase;
+    FastqRec R;
+    if (fastq_record(t.text, t.start, i, R)) { o.len1[read] = R.l_seq + 1; o.l_name[read] = R.l_name; atomicMax(&o.err[1], R.l_seq); }
+    else { o.len1[read] = 1; o.l_name[read] = 1; atomicMax(&o.err[0], (int32_t)(FASTQ_NO_ERROR - read)); }
+}
+
+// n bytes from src to dst by the G lanes of a group: the aligned 32-bit words of dst are assembled in a register and stored whole
+// (src is at any alignment), the bytes before the first and after the last singly -- as k_bam_emit stores a record
+template <int G>
+static __device__ inline void fastq_copy_bytes(uint8_t* dst, const uint8_t* src, int32_t n, int sub)
+{
+    const int32_t lead = (int32_t)((4 - ((uintptr_t)dst & 3)) & 3), head = n < lead ? n : lead;
+    const int32_t nw = (n - head) >> 2, tail = n - head - 4 * nw;
+    if (sub < head) dst[sub] = src[sub];
+    uint32_t* dw = (uint32_t*)(dst + head);
+    for (int32_t w = sub; w < nw; w += G) {
+        const uint8_t* s = src + head + 4 * w;
+        dw[w] = (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
+    }
+    if (sub < tail) dst[head + 4 * nw + sub] = src[head + 4 * nw + sub];
+}
+
+// (f) the lane groups of k_bam_emit: G lanes per record (8, or the wavefront for long reads) write its bases + NUL, its qualities +
+// NUL at the same offset, and its name.  Runs only after every record has passed its check: the places come from the line index,
+// the lengths from the scans.
+template <int G>
+__global__ void __launch_bounds__(256) k_fastq_copy(FastqText t, FastqOut o)
+{
+    const int i = blockIdx.x * (256 / G) + ((int)threadIdx.x / G), sub = (int)threadIdx.x % G;
+    if (i >= t.n_rec) return;
+    const int64_t read = (int64_t)t.stride * i + t.phase;
+    const int64_t so = o.seq_off[read], no = o.name_off[read];
+    const int64_t l_seq = o.seq_off[read + 1] - so - 1, l_name = o.name_off[read + 1] - no;
+    const int64_t name = t.start[4 * (int64_t)i] + 1, seq = t.start[4 * (int64_t)i + 1], qual = t.start[4 * (int64_t)i + 3];
+    if (l_seq < 0 || l_name < 0 || name + l_name > t.n || seq + l_seq > t.n || qual + l_seq > t.n) return;       // never outside the text
+    fastq_copy_bytes<G>(o.seq + so, t.text + seq, (int32_t)l_seq, sub);
+    fastq_copy_bytes<G>(o.qual + so, t.text + qual, (int32_t)l_seq, sub);
+    fastq_copy_bytes<G>(o.names + no, t.text + name, (int32_t)l_name, sub);
+    if (sub == 0) { o.seq[so + l_seq] = 0; o.qual[so + l_seq] = 0; }
 }
 
 // ------------------------------------------------------------------ BGZF members on the device (bgzf_deflate.h)
@@ -842,8 +963,41 @@ void launch_bam_size(hipStream_t st, const BamTile& t)
 void launch_bam_emit(hipStream_t st, const BamTile& t)
 {
     if (t.n_reads <= 0) return;
-    if (t.max_len > 1000) hipLaunchKernelGGL(k_bam_emit<64>, dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);      // long reads: a wavefront per read
-    else hipLaunchKernelGGL(k_bam_emit<8>, dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
+    if (t.max_len > 1000) {                                          // long reads: a wavefront per read
+        if (t.qual) hipLaunchKernelGGL((k_bam_emit<64, true>), dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((k_bam_emit<64, false>), dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);
+    } else if (t.qual) hipLaunchKernelGGL((k_bam_emit<8, true>), dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
+    else hipLaunchKernelGGL((k_bam_emit<8, false>), dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
+}
+
+void launch_qual_check(hipStream_t st, const uint8_t* raw, const uint8_t* qual, const int64_t* raw_off, int n_reads, int32_t* err)
+{
+    if (n_reads <= 0) return;
+    hipLaunchKernelGGL(k_qual_check, dim3((n_reads + 63) / 64), dim3(64), 0, st, raw, qual, raw_off, n_reads, err);
+}
+void launch_mate_names(hipStream_t st, const uint8_t* names, const int64_t* name_off, int n_pairs, int32_t* err)
+{
+    if (n_pairs <= 0) return;
+    hipLaunchKernelGGL(k_mate_names, dim3((n_pairs + 63) / 64), dim3(64), 0, st, names, name_off, n_pairs, err);
+}
+void launch_fastq_count(hipStream_t st, const uint8_t* text, int64_t n, int32_t* counts)
+{
+    hipLaunchKernelGGL(k_fastq_count, dim3((unsigned)fastq_n_chunks(n)), dim3(FASTQ_THREADS), 0, st, text, n, counts);
+}
+void launch_fastq_starts(hipStream_t st, const FastqText& t)
+{
+    hipLaunchKernelGGL(k_fastq_starts, dim3((unsigned)fastq_n_chunks(t.n)), dim3(FASTQ_THREADS), 0, st, t);
+}
+void launch_fastq_records(hipStream_t st, const FastqText& t, const FastqOut& o)
+{
+    if (t.n_rec <= 0) return;
+    hipLaunchKernelGGL(k_fastq_records, dim3((t.n_rec + 63) / 64), dim3(64), 0, st, t, o);
+}
+void launch_fastq_copy(hipStream_t st, const FastqText& t, const FastqOut& o, int max_len)
+{
+    if (t.n_rec <= 0) return;
+    if (max_len > 1000) hipLaunchKernelGGL(k_fastq_copy<64>, dim3((t.n_rec + 3) / 4), dim3(256), 0, st, t, o);     // long reads: a wavefront per read
+    else hipLaunchKernelGGL(k_fastq_copy<8>, dim3((t.n_rec + 31) / 32), dim3(256), 0, st, t, o);
 }
 
 void launch_post1(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv)

@@ -4,6 +4,7 @@
 #include "bwamem_types.h"
 #include "bam_encode.h"
 #include "bam_sort.h"
+#include "fastq_parse.h"
 
 void launch_build_occ64(hipStream_t st, const uint32_t* bwt, uint64_t n_blocks, uint4* occ);
 // suffix array at every ix.sa_intv-th rank (lo/hi, (seq_len >> sa_shift) + 1 entries) from the image's sampling; *err: device int, OR-ed on failure
@@ -34,6 +35,17 @@ void launch_pack(hipStream_t st, const TileView& tv, uint8_t* dst);
 // BAM records of a tile's packed response (bam_encode.h): sizes per read, then -- after a launch_scan over the batch -- the records
 void launch_bam_size(hipStream_t st, const BamTile& t);
 void launch_bam_emit(hipStream_t st, const BamTile& t);
+// Qualities and names of a batch: the qualities against the reads (a NUL where the read's is, else 33..126), and the names of the
+// two reads of every pair against each other.  err: one int, zeroed by the caller; FASTQ_NO_ERROR - the smallest offending read
+void launch_qual_check(hipStream_t st, const uint8_t* raw, const uint8_t* qual, const int64_t* raw_off, int n_reads, int32_t* err);
+void launch_mate_names(hipStream_t st, const uint8_t* names, const int64_t* name_off, int n_pairs, int32_t* err);
+// FASTQ text on the device (fastq_parse.h): _count the newlines of every chunk (fastq_n_chunks(n) ints), after a launch_scan
+// _starts writes the line index, _records checks every record and writes its read's lengths (o.err: two ints, zeroed by the
+// caller), and after two launch_scans _copy fills in bases, qualities and names (max_len: the longest read, o.err[1])
+void launch_fastq_count(hipStream_t st, const uint8_t* text, int64_t n, int32_t* counts);
+void launch_fastq_starts(hipStream_t st, const FastqText& t);
+void launch_fastq_records(hipStream_t st, const FastqText& t, const FastqOut& o);
+void launch_fastq_copy(hipStream_t st, const FastqText& t, const FastqOut& o, int max_len);
 // BGZF members of src[0, n) (bgzf_deflate.h): member i of input [i * 0xff00, ...) into slots + i * BGZF_SLOT and its size into
 // sizes[i], by `grid` = bgzf_grid(...) workgroups with bgzf_token_bytes(grid) of scratch; then -- after a launch_scan over the
 // sizes -- the members packed into out at off[i], followed by the 28-byte EOF block at off[n_blocks] when asked for

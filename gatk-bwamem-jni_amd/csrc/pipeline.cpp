@@ -373,6 +373,11 @@ struct bwamem_batch_s {
     DevBuf bam2, rec_cnt, rec_first, rec_src, rec_size, rec_psize, rec_dst, rec_scan_tmp;
     SortBufs srt;
     DevBuf bai_win_base, bai_win, bai_winv, bai_cnt, bai_start, bai_cid, bai_chunks;   // the index (bwamem_hip_batch_index_bam)
+    // what the records take from outside the response: base qualities laid out like d_raw (bwamem_hip_batch_set_qualities, or the
+    // FASTQ text), names of the batch's own (bwamem_hip_batch_upload_fastq) and the read group (bwamem_hip_batch_set_read_group)
+    DevBuf d_qual, own_names, own_name_off, d_rg;
+    bool has_qual = false, has_names = false;
+    std::string rg_line, rg_id;                      // rg_id empty: no read group
 };
 
 static const int LOG_TAB_N = 1 << 20;
@@ -1779,6 +1784,8 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
     if (!(b->bam_sizes.ensure(n * 4) && b->bam_off.ensure((n + 1) * 8) && b->bam_scan_tmp.ensure(scan_tmp_bytes((int64_t)n + 1)) && b->bam_err.ensure(64))) return false;
     HIP_OK(hipMemsetAsync(b->bam_sizes.p, 0, n * 4, ws.stream));       // reads no tile covers have no record
     HIP_OK(hipMemsetAsync(b->bam_err.p, 0, 64, ws.stream));
+    const bool own_names = !names && b->has_names;                     // a batch made from FASTQ text: its own names
+    if (own_names && paired) launch_mate_names(ws.stream, b->own_names.as<uint8_t>(), b->own_name_off.as<int64_t>(), (int)(n >> 1), b->bam_err.as<int32_t>() + 1);
     std::vector<BamTile> tiles;
     for (const TileOut& to : b->tiles) {
         if (!to.d_off || to.n_reads <= 0) continue;
@@ -1789,16 +1796,21 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
         t.raw = b->d_raw.as<uint8_t>(); t.raw_off = b->d_off.as<int64_t>() + r0;
         t.read_index0 = to.read_id; t.paired = paired != 0; t.n_seqs = ix->d.n_seqs;
         if (names) { t.names = b->bam_names.as<uint8_t>(); t.name_off = b->bam_name_off.as<int64_t>() + r0; }
+        else if (own_names) { t.names = b->own_names.as<uint8_t>(); t.name_off = b->own_name_off.as<int64_t>() + r0; }
+        if (b->has_qual) t.qual = b->d_qual.as<uint8_t>();
+        if (!b->rg_id.empty()) { t.rg = b->d_rg.as<uint8_t>(); t.l_rg = (int32_t)b->rg_id.size(); }
         t.sizes = b->bam_sizes.as<int32_t>() + r0; t.out_off = b->bam_off.as<int64_t>() + r0; t.out = nullptr; t.err = b->bam_err.as<int32_t>();
         tiles.push_back(t);
     }
     for (const BamTile& t : tiles) launch_bam_size(ws.stream, t);
     launch_scan(ws.stream, b->bam_sizes.as<int32_t>(), b->bam_off.as<int64_t>(), (int)n, b->bam_scan_tmp.as<int64_t>());
     HIP_OK(hipGetLastError());
-    int64_t total = 0; int32_t err = 0;
+    int64_t total = 0; int32_t errs[2] = { 0, 0 };                     // [1]: the mate-name check
     HIP_OK(hipMemcpyAsync(&total, b->bam_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, ws.stream));
-    HIP_OK(hipMemcpyAsync(&err, b->bam_err.p, 4, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(errs, b->bam_err.p, own_names && paired ? 8 : 4, hipMemcpyDeviceToHost, ws.stream));
     HIP_OK(hipStreamSynchronize(ws.stream));
+    int32_t err = errs[0]; const int32_t mate_err = errs[1];
+    if (mate_err) { fprintf(stderr, "[bwamem_hip] encode_bam: reads %d and %d are a pair but their names differ\n", FASTQ_NO_ERROR - mate_err, FASTQ_NO_ERROR - mate_err + 1); return false; }
     if (err & BAM_ERR_CIGAR_OPS) { fprintf(stderr, "[bwamem_hip] encode_bam: a record has more than %d CIGAR operations (not representable without the CG tag)\n", BAM_MAX_CIGAR_OPS); return false; }
     if (err || total < 0) { fprintf(stderr, "[bwamem_hip] encode_bam: the resident response does not parse (flags %d)\n", err); return false; }
     if (total == 0) { b->bam_encoded = true; return true; }
@@ -1810,6 +1822,154 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
     if (err) { fprintf(stderr, "[bwamem_hip] encode_bam: internal error while writing the records (flags %d)\n", err); return false; }
     b->bam_bytes = (size_t)total; b->bam_encoded = true;
     return true;
+}
+
+// ---- qualities, read group, and batches made from FASTQ text (bam_encode.h, fastq_parse.h; kernels next to the BAM kernels)
+// The device of b->idx is current and its lock held.  On failure the batch keeps the qualities it had.
+static bool set_qualities(bwamem_batch_s* b, const char* quals, size_t n_bytes)
+{
+    if (!quals) { b->has_qual = false; b->d_qual.reset(); return true; }
+    bwaidx_s* ix = b->idx;
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    if (b->h_payload || !b->d_raw.p) { fprintf(stderr, "[bwamem_hip] set_qualities: not a resident batch\n"); return false; }
+    if (n_bytes != b->n_bytes) { fprintf(stderr, "[bwamem_hip] set_qualities: %zu bytes of qualities for %zu bytes of reads (one string per read, each as long as its read)\n", n_bytes, b->n_bytes); return false; }
+    if (b->n_reads == 0) { b->has_qual = false; return true; }
+    DevBuf q, err;
+    if (!q.ensure(n_bytes + 64) || !err.ensure(64)) return false;
+    HIP_OK(hipMemcpyAsync(q.p, quals, n_bytes, hipMemcpyHostToDevice, ws.stream));
+    HIP_OK(hipMemsetAsync(err.p, 0, 64, ws.stream));
+    TIMED(ws, K_OTHER, launch_qual_check(ws.stream, b->d_raw.as<uint8_t>(), q.as<uint8_t>(), b->d_off.as<int64_t>(), (int)b->n_reads, err.as<int32_t>()));
+    int32_t e = 0;
+    HIP_OK(hipMemcpyAsync(&e, err.p, 4, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
+    timed_collect(ws);
+    if (e) { fprintf(stderr, "[bwamem_hip] set_qualities: the qualities of read %d are not a string of its length with every byte in 33..126\n", FASTQ_NO_ERROR - e); return false; }
+    b->d_qual = std::move(q); b->has_qual = true;
+    return true;
+}
+
+static bool set_read_group(bwamem_batch_s* b, const char* rg_line)
+{
+    if (!rg_line) { b->rg_line.clear(); b->rg_id.clear(); return true; }
+    const char* id = nullptr;
+    const int l_id = bam_rg_id(rg_line, &id);
+    if (l_id <= 0) { fprintf(stderr, "[bwamem_hip] set_read_group: not one \"@RG\\t\" line with an ID: field of 1..254 bytes\n"); return false; }
+    if (!b->d_rg.ensure(256)) return false;
+    HIP_OK(hipMemcpy(b->d_rg.p, id, (size_t)l_id, hipMemcpyHostToDevice));
+    b->rg_line = rg_line; b->rg_id.assign(id, (size_t)l_id);
+    return true;
+}
+
+// The texts go to HBM as they are; the kernels index their lines, check every record and lay out the payload bwamem_hip_batch_upload
+// would have built, the qualities next to it, and the names.  Two host waits: the line counts, then the totals.  The device of ix
+// is current and its lock held.  *made: the batch, or null with *bad set (malformed input); false: a device error.
+static bool upload_fastq(bwaidx_s* ix, const char* const text[2], const size_t n_text[2], int n_texts, int64_t* bad, bwamem_batch_s** made)
+{
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    *made = nullptr; *bad = -1;
+    DevBuf txt[2], counts[2], base[2], start[2], scan_tmp, len1, l_name, seq_off, name_off, err;
+    int64_t n_lines[2] = { 0, 0 };
+    size_t max_scan = 0;
+    for (int k = 0; k < n_texts; ++k) max_scan = std::max(max_scan, (size_t)fastq_n_chunks((int64_t)n_text[k]));
+    if (!scan_tmp.ensure(scan_tmp_bytes((int64_t)max_scan + 1))) return false;
+    for (int k = 0; k < n_texts; ++k) {
+        const int64_t n = (int64_t)n_text[k], nc = fastq_n_chunks(n);
+        if (!(txt[k].ensure((size_t)n + 16) && counts[k].ensure((size_t)nc * 4) && base[k].ensure(((size_t)nc + 1) * 8))) return false;
+        if (n) HIP_OK(hipMemcpyAsync(txt[k].p, text[k], (size_t)n, hipMemcpyHostToDevice, ws.stream));
+        TIMED(ws, K_OTHER, launch_fastq_count(ws.stream, txt[k].as<uint8_t>(), n, counts[k].as<int32_t>()));
+        TIMED(ws, K_OTHER, launch_scan(ws.stream, counts[k].as<int32_t>(), base[k].as<int64_t>(), (int)nc, scan_tmp.as<int64_t>()));
+        HIP_OK(hipMemcpyAsync(&n_lines[k], base[k].as<int64_t>() + nc, 8, hipMemcpyDeviceToHost, ws.stream));
+    }
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 1: the line counts
+    for (int k = 0; k < n_texts; ++k)
+        if (n_lines[k] < 0 || (n_lines[k] & 3)) { fprintf(stderr, "[bwamem_hip] upload_fastq: text %d has %lld lines, not a multiple of four\n", k + 1, (long long)n_lines[k]); timed_collect(ws); return true; }
+    if (n_texts == 2 && n_lines[0] != n_lines[1]) { fprintf(stderr, "[bwamem_hip] upload_fastq: %lld records in the first text, %lld in the second\n", (long long)(n_lines[0] >> 2), (long long)(n_lines[1] >> 2)); timed_collect(ws); return true; }
+    const int64_t n_rec = n_lines[0] >> 2, n_reads = n_rec * n_texts;
+    if (n_reads >= 0x7fffffff) { fprintf(stderr, "[bwamem_hip] upload_fastq: too many reads\n"); timed_collect(ws); return true; }
+    const size_t nr = (size_t)n_reads;
+    if (!(len1.ensure(nr * 4) && l_name.ensure(nr * 4) && seq_off.ensure((nr + 1) * 8) && name_off.ensure((nr + 1) * 8) && err.ensure(64)
+          && scan_tmp.ensure(scan_tmp_bytes(n_reads + 1)))) return false;
+    HIP_OK(hipMemsetAsync(err.p, 0, 64, ws.stream));
+    FastqText ft[2]; FastqOut fo; memset(&fo, 0, sizeof fo);
+    fo.len1 = len1.as<int32_t>(); fo.l_name = l_name.as<int32_t>(); fo.seq_off = seq_off.as<int64_t>(); fo.name_off = name_off.as<int64_t>(); fo.err = err.as<int32_t>();
+    for (int k = 0; k < n_texts; ++k) {
+        if (!start[k].ensure(((size_t)n_lines[k] + 1) * 8)) return false;
+        FastqText& t = ft[k];
+        t.text = txt[k].as<uint8_t>(); t.n = (int64_t)n_text[k]; t.chunk_base = base[k].as<int64_t>(); t.start = start[k].as<int64_t>(); t.n_lines = n_lines[k];
+        t.n_rec = (int32_t)n_rec; t.stride = n_texts; t.phase = k;
+        TIMED(ws, K_OTHER, launch_fastq_starts(ws.stream, t));
+        TIMED(ws, K_OTHER, launch_fastq_records(ws.stream, t, fo));
+    }
+    TIMED(ws, K_OTHER, launch_scan(ws.stream, len1.as<int32_t>(), seq_off.as<int64_t>(), (int)n_reads, scan_tmp.as<int64_t>()));
+    TIMED(ws, K_OTHER, launch_scan(ws.stream, l_name.as<int32_t>(), name_off.as<int64_t>(), (int)n_reads, scan_tmp.as<int64_t>()));
+    int32_t e[2] = { 0, 0 }; int64_t total = 0, total_names = 0;
+    HIP_OK(hipMemcpyAsync(e, err.p, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(&total, seq_off.as<int64_t>() + nr, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipMemcpyAsync(&total_names, name_off.as<int64_t>() + nr, 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 2: the totals
+    if (e[0]) {
+        *bad = FASTQ_NO_ERROR - e[0];
+        fprintf(stderr, "[bwamem_hip] upload_fastq: read %lld: not a four-line record ('@' name of 1..254 bytes, bases, '+', as many qualities in 33..126)\n", (long long)*bad);
+        timed_collect(ws); return true;
+    }
+    if (total < n_reads || total_names < n_reads || total >= ((int64_t)1 << 31)) { fprintf(stderr, "[bwamem_hip] upload_fastq: the reads do not fit one request\n"); timed_collect(ws); return true; }
+    std::unique_ptr<bwamem_batch_s> b(new bwamem_batch_s());
+    b->idx = ix; b->n_reads = (uint32_t)n_reads; b->n_bytes = (size_t)total;
+    b->h_off.assign(nr + 1, 0);
+    if (!(b->d_raw.ensure((size_t)total + 64) && b->d_seq.ensure((size_t)total + 64) && b->d_qual.ensure((size_t)total + 64) && b->own_names.ensure((size_t)total_names + 8))) return false;
+    fo.seq = b->d_raw.as<uint8_t>(); fo.qual = b->d_qual.as<uint8_t>(); fo.names = b->own_names.as<uint8_t>();
+    for (int k = 0; k < n_texts; ++k) TIMED(ws, K_OTHER, launch_fastq_copy(ws.stream, ft[k], fo, e[1]));
+    if (n_texts == 2) {
+        HIP_OK(hipMemsetAsync(err.p, 0, 4, ws.stream));
+        TIMED(ws, K_OTHER, launch_mate_names(ws.stream, fo.names, fo.name_off, (int)n_rec, fo.err));
+        HIP_OK(hipMemcpyAsync(e, err.p, 4, hipMemcpyDeviceToHost, ws.stream));
+    }
+    HIP_OK(hipMemcpyAsync(b->h_off.data(), seq_off.p, (nr + 1) * 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));
+    timed_collect(ws);
+    if (n_texts == 2 && e[0]) { *bad = FASTQ_NO_ERROR - e[0]; fprintf(stderr, "[bwamem_hip] upload_fastq: reads %lld and %lld are a pair but their names differ\n", (long long)*bad, (long long)*bad + 1); return true; }
+    b->d_off = std::move(seq_off); b->own_name_off = std::move(name_off);
+    b->has_qual = b->has_names = true;
+    *made = b.release();
+    return true;
+}
+
+int bwamem_hip_batch_set_qualities(bwamem_batch_t* b, const char* quals, size_t nBytes)
+{
+    return guarded("bwamem_hip_batch_set_qualities", -1, [&]() -> int {
+        if (!b || !b->idx) return -1;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+        return set_qualities(b, quals, nBytes) ? 0 : -1;
+    });
+}
+
+int bwamem_hip_batch_set_read_group(bwamem_batch_t* b, const char* rg_line)
+{
+    return guarded("bwamem_hip_batch_set_read_group", -1, [&]() -> int {
+        if (!b || !b->idx) return -1;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+        return set_read_group(b, rg_line) ? 0 : -1;
+    });
+}
+
+bwamem_batch_t* bwamem_hip_batch_upload_fastq(bwaidx_t* idx, const char* text1, size_t n1, const char* text2, size_t n2, int64_t* bad_record)
+{
+    if (bad_record) *bad_record = -1;
+    return guarded("bwamem_hip_batch_upload_fastq", (bwamem_batch_t*)0, [&]() -> bwamem_batch_t* {
+        if (!idx || (!text1 && n1) || (!text2 && n2)) return 0;
+        if (n1 >= ((size_t)1 << 31) || n2 >= ((size_t)1 << 31) || n1 + n2 >= ((size_t)1 << 31)) { fprintf(stderr, "[bwamem_hip] upload_fastq: a call is one request under 2 GiB\n"); return 0; }
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (hipSetDevice(idx->device) != hipSuccess) return 0;
+        const char* const text[2] = { text1, text2 }; const size_t n_text[2] = { n1, n2 };
+        int64_t bad = -1; bwamem_batch_s* made = nullptr;
+        if (!upload_fastq(idx, text, n_text, text2 ? 2 : 1, &bad, &made)) return 0;
+        if (!made && bad_record) *bad_record = bad;
+        return made;
+    });
 }
 
 int bwamem_hip_batch_keep_offsets(bwamem_batch_t* b, int on)

@@ -9,6 +9,8 @@
 //     0x61/0x63/0x91/0x93 on the response itself);
 //   * records after a read's first one turn soft clips into hard clips and carry only the aligned bases (upstream without -Y);
 //   * SEQ is the read as sequenced for forward alignments, its reverse complement for reverse ones; QUAL is '*' (the request has none);
+//     bwamem_hip_response_to_sam_q takes the qualities next to the request and writes them in the order of SEQ (reversed, clipped),
+//     and ends every line with RG:Z:<ID> when given a read group;
 //   * RNEXT/PNEXT/TLEN from the record's mate fields ("=" for the same contig); unmapped reads of a pair take their mate's place;
 //   * tags NM:i MD:Z AS:i XS:i and XA:Z when the record has them.
 // Read names: supplied by the caller, else "r<index>" (paired: "p<pair index>" for both mates).
@@ -199,7 +201,9 @@ char* bwamem_hip_sam_header(bwaidx_t* idx, size_t* pBytes)
     } catch (...) { return 0; }
 }
 
-char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired, size_t* pBytes)
+// quals: the reads' Phred+33 strings back to back, NUL-terminated like the request's reads, or null; rg_id: a read group's ID, or null
+static char* response_to_sam(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired,
+                             const char* quals, const char* rg_id, size_t* pBytes)
 {
     if (pBytes) *pBytes = 0;
     if (!idx || !pSeq || !response) return 0;
@@ -207,6 +211,7 @@ char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* re
         const std::vector<ContigInfo>& contigs = bwamem_index_contigs(idx);
         uint32_t n_reads; memcpy(&n_reads, pSeq, 4);
         const char* q = pSeq + 4;
+        const char* ql = quals;
         const uint8_t* p = (const uint8_t*)response;
         const uint8_t* const end = p + responseBytes;
         Out o;
@@ -216,6 +221,8 @@ char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* re
             const size_t l_seq = strlen(q);
             const char* seq = q;
             q += l_seq + 1;
+            const char* qual = ql;
+            if (ql) { if (strlen(ql) != l_seq) return 0; ql += l_seq + 1; }
             std::string name;
             if (readNames && readNames[r]) name = readNames[r];
             else { char b[32]; snprintf(b, sizeof b, paired ? "p%u" : "r%u", paired ? r >> 1 : r); name = b; }
@@ -273,7 +280,10 @@ char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* re
                 if (l_seq == 0) o.ch('*');
                 else if (flag & 0x10) { for (size_t i = b; i < e; ++i) o.ch(comp(seq[l_seq - 1 - i])); }
                 else o.s.append(seq + b, e - b);
-                o.put("\t*");
+                o.ch('\t');
+                if (!qual || e == b) o.ch('*');
+                else if (flag & 0x10) { for (size_t i = b; i < e; ++i) o.ch(qual[l_seq - 1 - i]); }
+                else o.s.append(qual + b, e - b);
                 if (!(flag & 4)) {
                     o.put("\tNM:i:"); o.num(nm);
                     if (!md.empty()) { o.put("\tMD:Z:"); o.put(md); }
@@ -281,6 +291,7 @@ char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* re
                     if (xs >= 0) { o.put("\tXS:i:"); o.num(xs); }
                     if (!xa.empty()) { o.put("\tXA:Z:"); o.put(xa); }
                 }
+                if (rg_id) { o.put("\tRG:Z:"); o.put(rg_id); }
                 o.ch('\n');
             }
         }
@@ -290,6 +301,51 @@ char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* re
         memcpy(res, o.s.data(), o.s.size() + 1);
         if (pBytes) *pBytes = o.s.size();
         return res;
+    } catch (...) { return 0; }
+}
+
+char* bwamem_hip_response_to_sam(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired, size_t* pBytes)
+{
+    return response_to_sam(idx, pSeq, response, responseBytes, readNames, paired, nullptr, nullptr, pBytes);
+}
+
+char* bwamem_hip_response_to_sam_q(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired,
+                                   const char* quals, const char* rgId, size_t* pBytes)
+{
+    return response_to_sam(idx, pSeq, response, responseBytes, readNames, paired, quals, rgId, pBytes);
+}
+
+// header text with the read group's line after the last @SQ line; false: the line is refused
+static bool header_text_rg(const char* text, size_t l_text, const char* rg_line, std::string& out)
+{
+    const char* id = nullptr;
+    if (bam_rg_id(rg_line, &id) <= 0) { fprintf(stderr, "[bwamem_hip] header: not one \"@RG\\t\" line with an ID: field of 1..254 bytes\n"); return false; }
+    size_t at = 0, after_sq = 0;
+    while (at < l_text) {
+        const char* eol = (const char*)memchr(text + at, '\n', l_text - at);
+        const size_t next = eol ? (size_t)(eol - text) + 1 : l_text;
+        if (next - at >= 3 && !memcmp(text + at, "@SQ", 3)) after_sq = next;
+        at = next;
+    }
+    out.assign(text, after_sq); out += rg_line; out += '\n'; out.append(text + after_sq, l_text - after_sq);
+    return true;
+}
+
+char* bwamem_hip_sam_header_rg(bwaidx_t* idx, const char* rg_line, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    try {
+        size_t l_text = 0;
+        Freed text(bwamem_hip_sam_header(idx, &l_text));
+        if (!text.p) return 0;
+        std::string o;
+        if (!rg_line) o.assign((const char*)text.p, l_text);
+        else if (!header_text_rg((const char*)text.p, l_text, rg_line, o)) return 0;
+        char* r = (char*)malloc(o.size() + 1);
+        if (!r) return 0;
+        memcpy(r, o.c_str(), o.size() + 1);
+        if (pBytes) *pBytes = o.size();
+        return r;
     } catch (...) { return 0; }
 }
 
@@ -437,6 +493,71 @@ void* bwamem_hip_bam_header_sorted(bwaidx_t* idx, size_t* pBytes)
     } catch (...) { return 0; }
 }
 
+// bwamem_hip_bam_header / _sorted with the read group's line after the last @SQ line (rg_line == null: the header as it is)
+void* bwamem_hip_bam_header_rg(bwaidx_t* idx, int sorted, const char* rg_line, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    try {
+        size_t n = 0;
+        Freed hdr(sorted ? bwamem_hip_bam_header_sorted(idx, &n) : bwamem_hip_bam_header(idx, &n));
+        if (!hdr.p || n < 8) return 0;
+        const uint8_t* h = (const uint8_t*)hdr.p;
+        const size_t l_text = (size_t)h[4] | (size_t)h[5] << 8 | (size_t)h[6] << 16 | (size_t)h[7] << 24;
+        if (l_text > n - 8) return 0;
+        std::string text;
+        if (!rg_line) text.assign((const char*)h + 8, l_text);
+        else if (!header_text_rg((const char*)h + 8, l_text, rg_line, text)) return 0;
+        if (text.size() > 0x7fffffff) return 0;
+        std::string o("BAM\1", 4);
+        uint8_t b[4]; le32(b, (uint32_t)text.size());
+        o.append((const char*)b, 4); o += text; o.append((const char*)h + 8 + l_text, n - 8 - l_text);
+        void* r = malloc(o.size());
+        if (!r) return 0;
+        memcpy(r, o.data(), o.size());
+        if (pBytes) *pBytes = o.size();
+        return r;
+    } catch (...) { return 0; }
+}
+
+}  // extern "C"
+
+namespace {
+
+// An aligned batch to a file, everything on the device: encode (names: the caller's, or null), sort if asked, compress, index if
+// asked (fd_bai >= 0), write.  The header carries rg_line when there is one.  Everything is made before the first byte is written.
+int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off, const char* rg_line, int sort, int fd, int fd_bai,
+                      int write_header)
+{
+    if (bwamem_hip_batch_encode_bam(b, paired, names, name_off) != 0) return -1;
+    if (sort && bwamem_hip_batch_sort_bam(b) != 0) return -1;
+    size_t nh = 0, nzh = 0, nz = 0, nb = 0;
+    Freed zh, z, bai;
+    if (write_header) {
+        Freed hdr(bwamem_hip_bam_header_rg(idx, sort, rg_line, &nh));
+        if (!hdr.p) return -1;
+        zh.p = bwamem_hip_bgzf_compress_device(idx, hdr.p, nh, 0, &nzh);
+        if (!zh.p) return -1;
+    }
+    if (bwamem_hip_batch_bam_bytes(b) != 0) {
+        if (bwamem_hip_batch_compress_bam(b, 1) != 0) return -1;
+        nz = bwamem_hip_batch_bgzf_bytes(b);
+        z.p = malloc(nz ? nz : 1);
+        if (!z.p || bwamem_hip_batch_bgzf_download(b, z.p) != 0) return -1;
+    }
+    if (fd_bai >= 0) {
+        bai.p = bwamem_hip_batch_index_bam(b, (int64_t)nzh, &nb);
+        if (!bai.p) return -1;
+    }
+    if (write_header && !write_all(fd, (const uint8_t*)zh.p, nzh)) return -1;
+    if (z.p ? !write_all(fd, (const uint8_t*)z.p, nz) : !write_all(fd, BGZF_EOF, sizeof BGZF_EOF)) return -1;      // no record: the EOF block alone
+    if (fd_bai >= 0 && !write_all(fd_bai, (const uint8_t*)bai.p, nb)) return -1;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
 // bwamem_hip_align_to_bam_device with the records coordinate-sorted on the device, and the BAI index into fd_bai when asked for
 int bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
                                    int fd, int fd_bai, int write_header)
@@ -456,31 +577,26 @@ int bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const me
         BatchOwner bo{ bwamem_hip_batch_upload(idx, pSeq, nBytes) };
         if (!bo.b) return -1;
         if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
-        if (bwamem_hip_batch_encode_bam(bo.b, paired, readNames ? blob.data() : nullptr, readNames ? name_off.data() : nullptr) != 0) return -1;
-        if (bwamem_hip_batch_sort_bam(bo.b) != 0) return -1;
-        // everything is made before the first byte is written
-        size_t nh = 0, nzh = 0, nz = 0, nb = 0;
-        Freed zh, z, bai;
-        if (write_header) {
-            Freed hdr(bwamem_hip_bam_header_sorted(idx, &nh));
-            if (!hdr.p) return -1;
-            zh.p = bwamem_hip_bgzf_compress_device(idx, hdr.p, nh, 0, &nzh);
-            if (!zh.p) return -1;
-        }
-        if (bwamem_hip_batch_bam_bytes(bo.b) != 0) {
-            if (bwamem_hip_batch_compress_bam(bo.b, 1) != 0) return -1;
-            nz = bwamem_hip_batch_bgzf_bytes(bo.b);
-            z.p = malloc(nz ? nz : 1);
-            if (!z.p || bwamem_hip_batch_bgzf_download(bo.b, z.p) != 0) return -1;
-        }
-        if (fd_bai >= 0) {
-            bai.p = bwamem_hip_batch_index_bam(bo.b, (int64_t)nzh, &nb);
-            if (!bai.p) return -1;
-        }
-        if (write_header && !write_all(fd, (const uint8_t*)zh.p, nzh)) return -1;
-        if (z.p ? !write_all(fd, (const uint8_t*)z.p, nz) : !write_all(fd, BGZF_EOF, sizeof BGZF_EOF)) return -1;      // no record: the EOF block alone
-        if (fd_bai >= 0 && !write_all(fd_bai, (const uint8_t*)bai.p, nb)) return -1;
-        return 0;
+        return batch_to_bam_file(idx, bo.b, paired, readNames ? blob.data() : nullptr, readNames ? name_off.data() : nullptr, nullptr, 1, fd, fd_bai, write_header);
+    } catch (...) { return -1; }
+}
+
+// FASTQ text in, a BAM file out: the text is taken apart on the device (fastq_parse.h), so the records carry the reads' own names and
+// base qualities, and RG:Z when rg_line names a read group
+int bwamem_hip_align_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
+                                  const char* rg_line, int sort, int fd, int fd_bai, int write_header)
+{
+    try {
+        if (!idx || !opt || fd < 0) return -1;
+        if (fd_bai >= 0 && !(sort && write_header)) { fprintf(stderr, "[bwamem_hip] align_fastq_to_bam: an index needs a sorted file with its header\n"); return -1; }
+        int32_t flag; memcpy(&flag, (const char*)opt + 60, 4);                  // mem_opt_t.flag (BwaMemAligner.java:75)
+        const int paired = (flag & 0x2) != 0;
+        int64_t bad = -1;
+        BatchOwner bo{ bwamem_hip_batch_upload_fastq(idx, text1, n1, text2, n2, &bad) };
+        if (!bo.b) return -1;
+        if (rg_line && bwamem_hip_batch_set_read_group(bo.b, rg_line) != 0) return -1;
+        if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
+        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, sort, fd, fd_bai, write_header);
     } catch (...) { return -1; }
 }
 

@@ -183,6 +183,41 @@ int    bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const
                                       const char* const* readNames, int fd, int fd_bai, int write_header);
 int    bwamem_hip_sort_pairs_device(bwaidx_t* idx, const uint64_t* keys, size_t n, uint32_t* perm);
 
+/* FASTQ in, base qualities and read groups out (csrc/fastq_parse.h, csrc/bam_encode.h; additive).  Qualities and read names never
+ * touch the alignment; they only have to be resident when the records are written.  So FASTQ text is uploaded as it is and taken
+ * apart by HIP kernels -- a line index, one lane per record to check it, a copy -- and the host never looks at its bytes.  Without
+ * qualities, a read group or a FASTQ call every entry point above produces byte for byte what it did.
+ *   _set_qualities  before _encode_bam: quals = nReads NUL-terminated Phred+33 strings in request order (host memory), the string of
+ *                   read i exactly as long as read i, nBytes = their size -- the layout of the request's payload.  Checked on the
+ *                   device (a NUL where each read's NUL is, every other byte in 33..126); non-zero with a message otherwise, and the
+ *                   batch keeps the qualities it had.  quals == NULL removes them.  QUAL of a record: csrc/bam_encode.h.
+ *   _set_read_group before _encode_bam: rg_line = one header line without its newline; it must begin with "@RG\t", contain an ID:
+ *                   field of 1..254 bytes and no '\n' or '\r'; non-zero otherwise.  Every record, unmapped ones included, then ends
+ *                   with the tag RG:Z:<ID> (after XA).  NULL removes the read group.
+ *   bwamem_hip_bam_header_rg / bwamem_hip_sam_header_rg   bwamem_hip_bam_header (sorted != 0: _sorted) / bwamem_hip_sam_header with
+ *                   rg_line after the last @SQ line (NULL: the header as it is); NULL when the line is refused.  jnibwa_free.
+ *   bwamem_hip_response_to_sam_q   bwamem_hip_response_to_sam with the qualities (the format above, or NULL: '*') and a read group's
+ *                   ID (or NULL: no tag).  A BAM record decodes to exactly this line, QUAL and RG:Z included.
+ *   _upload_fastq   a batch from FASTQ text (rules: csrc/fastq_parse.h -- four lines per record, "\n" or "\r\n", names up to the first
+ *                   blank with a trailing /1 or /2 removed).  text2 == NULL: single-end reads or one interleaved file (the paired flag
+ *                   of _encode_bam decides); with both texts read 2i comes from text1 and read 2i + 1 from text2, and their names must
+ *                   be equal.  The batch holds the payload and offsets bwamem_hip_batch_upload would have built from the same reads,
+ *                   the reads' names and their qualities: _encode_bam(b, paired, NULL, NULL) then writes those names instead of
+ *                   "r<index>" (paired: the names of the two reads of a pair must be equal, else non-zero).  Malformed input: NULL
+ *                   with a message, and *bad_record = the smallest index of an offending read (see fastq_parse.h), or -1 for errors
+ *                   of no single record (a line count that is no multiple of four, unequal record counts).
+ *   bwamem_hip_align_fastq_to_bam   upload_fastq, align, encode, sort if asked, compress on the device, index if fd_bai >= 0 (needs
+ *                   sort and write_header), write; rg_line (or NULL) goes into the header and onto every record.  0 = ok. */
+int    bwamem_hip_batch_set_qualities(bwamem_batch_t* b, const char* quals, size_t nBytes);
+int    bwamem_hip_batch_set_read_group(bwamem_batch_t* b, const char* rg_line);
+void*  bwamem_hip_bam_header_rg(bwaidx_t* idx, int sorted, const char* rg_line, size_t* pBytes);   /* jnibwa_free */
+char*  bwamem_hip_sam_header_rg(bwaidx_t* idx, const char* rg_line, size_t* pBytes);               /* jnibwa_free */
+char*  bwamem_hip_response_to_sam_q(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired,
+                                    const char* quals, const char* rgId, size_t* pBytes);
+bwamem_batch_t* bwamem_hip_batch_upload_fastq(bwaidx_t* idx, const char* text1, size_t n1, const char* text2, size_t n2, int64_t* bad_record);
+int    bwamem_hip_align_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
+                                     const char* rg_line, int sort, int fd, int fd_bai, int write_header);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
