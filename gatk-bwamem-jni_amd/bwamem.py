@@ -64,6 +64,22 @@ _lib.bwamem_hip_align_fastq_to_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _
 _BGZF_EOF = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0])
 
 
+class _DupCounts(ctypes.Structure):
+    """bwamem_dup_counts_t"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("unpaired_reads_examined", "read_pairs_examined", "secondary_or_supplementary", "unmapped_reads",
+                                               "unpaired_read_duplicates", "read_pair_duplicates")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+_lib.bwamem_hip_batch_mark_duplicates.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(_DupCounts)]
+_lib.bwamem_hip_align_to_marked_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(_DupCounts)]
+_lib.bwamem_hip_align_fastq_to_marked_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.POINTER(_DupCounts)]
+
+
 def _taken(p, n):
     out = ctypes.string_at(p, n)
     _lib.jnibwa_free(p)
@@ -352,7 +368,7 @@ class BwaMemAligner:
             self.index.deRefIndex()
 
     def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False, sort=False, index_path=None, quals=None,
-                       read_group=None):
+                       read_group=None, mark_duplicates=False):
         """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
         `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
         "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred).
@@ -361,27 +377,40 @@ class BwaMemAligner:
         sort=True (implies device=True): the records are coordinate-sorted on the device within this call and the header says
         SO:coordinate; index_path: the BAI index of that file is written there as well (needs sort=True).
         quals: one Phred+33 string per sequence, each as long as its sequence: the records carry them as QUAL.  read_group: an
-        "@RG\\tID:..." header line: it goes into the header, and every record carries RG:Z:<ID>.  Either implies device=True."""
+        "@RG\\tID:..." header line: it goes into the header, and every record carries RG:Z:<ID>.  Either implies device=True.
+        mark_duplicates=True (needs device=True, sort=True, quals or read_group: the records have to stay on the device): duplicates
+        are marked on the device within this call before the sort (csrc/bam_dup.h), and the counts are returned as a dict."""
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
+        if mark_duplicates and not (device or sort or quals is not None or read_group is not None):
+            raise ValueError("mark_duplicates needs device=True or sort=True: the host-framing path takes the records off the device unmarked")
         opts = self._getOpts()
         seqs = [func(e) for e in sequences]
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
         if names is not None and len(names) != len(seqs):
             raise ValueError("%d names for %d sequences" % (len(names), len(seqs)))
         if quals is not None or read_group is not None:
-            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group)
+            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group, mark_duplicates)
         buf = struct.pack("=i", len(seqs)) + b"".join(s + b"\0" for s in seqs)
         arr = None
         if names is not None:
             arr = (ctypes.c_char_p * len(names))(*[n.encode() if isinstance(n, str) else bytes(n) for n in names])
         pes = self.pairEndStats
         pb = ctypes.create_string_buffer(pes._pack(), 128) if pes is not None else None
+        counts = _DupCounts()
         self.index.refIndex()
         try:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             try:
-                if sort:
+                if mark_duplicates:
+                    fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
+                    try:
+                        rc = _lib.bwamem_hip_align_to_marked_bam(self.index.indexAddress, opts, pb, buf, len(buf), arr, 1 if sort else 0, fd, fd_bai, 1,
+                                                                 ctypes.byref(counts))
+                    finally:
+                        if fd_bai >= 0:
+                            os.close(fd_bai)
+                elif sort:
                     fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
                     try:
                         rc = _lib.bwamem_hip_align_to_sorted_bam(self.index.indexAddress, opts, pb, buf, len(buf), arr, fd, fd_bai, 1)
@@ -398,8 +427,9 @@ class BwaMemAligner:
             self.index.deRefIndex()
         if rc != 0:
             raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s" % (self.index.indexImageFile, path))
+        return counts.as_dict() if mark_duplicates else None
 
-    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group):
+    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group, mark_duplicates=False):
         """alignSeqsToBam through the batch calls, which take qualities and a read group; nothing is written unless all of it succeeds"""
         if quals is not None:
             quals = [q.encode() if isinstance(q, str) else bytes(q) for q in quals]
@@ -432,7 +462,12 @@ class BwaMemAligner:
                 raise ValueError("the read group was refused: one '@RG\\t' line with an ID: field of 1..254 bytes")
             if _lib.bwamem_hip_batch_keep_offsets(b, 1) != 0 or _lib.bwamem_hip_batch_align(idx, self._getOpts(), pb, b, 0) != 0:
                 raise fail
-            if _lib.bwamem_hip_batch_encode_bam(b, paired, blob, off) != 0 or (sort and _lib.bwamem_hip_batch_sort_bam(b) != 0):
+            counts = _DupCounts()
+            if _lib.bwamem_hip_batch_encode_bam(b, paired, blob, off) != 0:
+                raise fail
+            if mark_duplicates and _lib.bwamem_hip_batch_mark_duplicates(b, paired, ctypes.byref(counts)) != 0:
+                raise fail
+            if sort and _lib.bwamem_hip_batch_sort_bam(b) != 0:
                 raise fail
             sz = ctypes.c_size_t()
             p = _lib.bwamem_hip_bam_header_rg(idx, 1 if sort else 0, rg, ctypes.byref(sz))
@@ -464,12 +499,15 @@ class BwaMemAligner:
         if bai is not None:
             with open(index_path, "wb") as f:
                 f.write(bai)
+        return counts.as_dict() if mark_duplicates else None
 
-    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None):
+    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False):
         """Additive: FASTQ in, a BAM file out.  fastq1 / fastq2: FASTQ text (bytes), or the path of an uncompressed FASTQ file (str);
         with fastq2 the two hold the first and second reads of the pairs, without it fastq1 holds single-end reads or -- after
         alignPairs() -- interleaved pairs.  The text is taken apart on the device: the records carry the reads' names and base
-        qualities, and RG:Z:<ID> when read_group (an "@RG\\tID:..." header line) is given.  sort / index_path as alignSeqsToBam."""
+        qualities, and RG:Z:<ID> when read_group (an "@RG\\tID:..." header line) is given.  sort / index_path as alignSeqsToBam.
+        mark_duplicates=True: duplicates are marked on the device within this call, before the sort (csrc/bam_dup.h -- the highest
+        sum of base qualities keeps a group's place), and the counts are returned as a dict."""
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
         opts = self._getOpts()
@@ -483,12 +521,17 @@ class BwaMemAligner:
         rg = None if read_group is None else read_group.encode() if isinstance(read_group, str) else bytes(read_group)
         pes = self.pairEndStats
         pb = ctypes.create_string_buffer(pes._pack(), 128) if pes is not None else None
+        counts = _DupCounts()
         idx = self.index.refIndex()
         try:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
             try:
-                rc = _lib.bwamem_hip_align_fastq_to_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, rg, 1 if sort else 0, fd, fd_bai, 1)
+                if mark_duplicates:
+                    rc = _lib.bwamem_hip_align_fastq_to_marked_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, rg, 1 if sort else 0, fd, fd_bai, 1,
+                                                                   ctypes.byref(counts))
+                else:
+                    rc = _lib.bwamem_hip_align_fastq_to_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, rg, 1 if sort else 0, fd, fd_bai, 1)
             finally:
                 os.close(fd)
                 if fd_bai >= 0:
@@ -497,6 +540,7 @@ class BwaMemAligner:
             self.index.deRefIndex()
         if rc != 0:
             raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s (malformed FASTQ, or a device error)" % (self.index.indexImageFile, path))
+        return counts.as_dict() if mark_duplicates else None
 
     def alignSeqs(self, sequences, func=lambda s: s):
         """BwaMemAligner.java:192-310: one list of BwaMemAlignment per input sequence"""

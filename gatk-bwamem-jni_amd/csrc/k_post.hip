@@ -889,6 +889,174 @@ __global__ void __launch_bounds__(256) k_bai_windows(const int32_t* win, int n_w
     if (w < n_win) out[w] = win[w] < 0 ? SORT_KEY_LAST : bai_voffset(member_off, coffset0, rec_off[n_rec - 1 - win[w]]);
 }
 
+// ------------------------------------------------------------------ duplicate marking between the encoder and the sort (bam_dup.h)
+// a lane's count, added up over the wavefront, into *dst by one lane (every lane of the wavefront calls this)
+static __device__ inline void dup_wave_add(int v, int32_t* dst)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (((int)threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
+}
+
+// (a) one lane per template walks the records of its reads along block_size, as k_bamrec_count does: the primaries, their ends from
+// the records' own CIGARs, the fragment and pair keys, is_paired, the place of QUAL, the counts.  A template with an error has no entry.
+__global__ void __launch_bounds__(64) k_dup_entries(DupView v)
+{
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    int n_unpaired = 0, n_pair = 0, n_sec = 0, n_unmapped = 0, max_len = 0, err = 0;
+    if (t < v.n_tmpl) {
+        const int r0 = v.paired ? 2 * t : t, nr = v.paired && r0 + 1 < v.n_reads ? 2 : 1;
+        DupEnd e[2];
+        bool has[2] = { false, false };
+        for (int k = 0; k < nr && !err; ++k) {
+            int64_t o = v.bam_off[r0 + k];
+            const int64_t hi = v.bam_off[r0 + k + 1];
+            bool primary = false;
+            while (o < hi) {
+                if (hi - o < BAMSORT_MIN_REC) { err = BAMDUP_ERR_WALK; break; }
+                const int64_t size = 4 + (int64_t)(int32_t)bamsort_ld32(v.bam + o);
+                if (size < BAMSORT_MIN_REC || size > hi - o) { err = BAMDUP_ERR_WALK; break; }
+                const uint32_t flag = dup_ld16(v.bam + o + 18);
+                if (flag & 0x900) ++n_sec;
+                else if (primary) { err = BAMDUP_ERR_PRIMARY; break; }
+                else {
+                    primary = true;
+                    if (flag & 4) ++n_unmapped;
+                    else {
+                        err = dup_end(v.bam + o, size, o, e[k]);
+                        if (err) break;
+                        has[k] = true;
+                    }
+                }
+                o += size;
+            }
+        }
+        if (err) { has[0] = has[1] = false; n_sec = n_unmapped = 0; }
+        for (int k = 0; k < nr; ++k) {
+            const bool p = has[k] && (e[k].flag & 1) && !(e[k].flag & 8);
+            v.frag_end[r0 + k] = has[k] ? e[k].key : SORT_KEY_LAST;
+            v.qual_off[r0 + k] = has[k] ? e[k].qual_off : 0;
+            v.l_seq[r0 + k] = has[k] ? e[k].l_seq : 0;
+            v.is_paired[r0 + k] = p ? 1 : 0;
+            if (has[k] && !p) ++n_unpaired;
+            if (has[k] && e[k].l_seq > max_len) max_len = e[k].l_seq;
+        }
+        if (v.paired) {
+            const bool both = has[0] && has[1];
+            v.pair_a[t] = !both ? SORT_KEY_LAST : e[0].key < e[1].key ? e[0].key : e[1].key;
+            v.pair_b[t] = !both ? SORT_KEY_LAST : e[0].key < e[1].key ? e[1].key : e[0].key;
+            n_pair = both ? 1 : 0;
+        }
+    }
+    dup_wave_add(n_unpaired, &v.cnt[DUP_CNT_UNPAIRED]);
+    dup_wave_add(n_pair, &v.cnt[DUP_CNT_PAIRS]);
+    dup_wave_add(n_sec, &v.cnt[DUP_CNT_SECONDARY]);
+    dup_wave_add(n_unmapped, &v.cnt[DUP_CNT_UNMAPPED]);
+    for (int o = 32; o > 0; o >>= 1) { const int m = __shfl_xor(max_len, o); max_len = m > max_len ? m : max_len; err |= __shfl_xor(err, o); }
+    if (((int)threadIdx.x & 63) == 0) {
+        if (max_len) atomicMax(&v.cnt[DUP_CNT_MAX_LEN], max_len);
+        if (err) atomicOr(&v.cnt[DUP_CNT_ERR], err);
+    }
+}
+
+// (b) the scores, by the lane groups of k_bam_emit: G lanes per read (8, or the wavefront for long reads) share out the aligned
+// 32-bit words of QUAL, take the up to three bytes before the first and after the last singly, and add up within the group
+template <int G>
+__global__ void __launch_bounds__(256) k_dup_scores(DupView v)
+{
+    const int r = blockIdx.x * (256 / G) + ((int)threadIdx.x / G), sub = (int)threadIdx.x % G;
+    int32_t s = 0;
+    if (r < v.n_reads) {
+        const int32_t n = v.l_seq[r];
+        const uint8_t* q = v.bam + v.qual_off[r];
+        const int32_t lead = (int32_t)((4 - ((uintptr_t)q & 3)) & 3), head = n < lead ? n : lead;
+        const int32_t nw = (n - head) >> 2, tail = n - head - 4 * nw;
+        if (sub < head) s += dup_qual(q[sub]);
+        const uint32_t* w = (const uint32_t*)(q + head);
+        for (int32_t k = sub; k < nw; k += G) s += dup_qual4(w[k]);
+        if (sub < tail) s += dup_qual(q[head + 4 * nw + sub]);
+    }
+    for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    if (r < v.n_reads && sub == 0) v.score[r] = s > DUP_SCORE_CAP ? DUP_SCORE_CAP : s;
+}
+
+// (c) the first sort keys: the read's score under is_paired, the template's score
+__global__ void __launch_bounds__(256) k_dup_score_keys(DupView v, uint64_t* frag_key, uint64_t* pair_key)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < v.n_reads) frag_key[i] = v.frag_end[i] == SORT_KEY_LAST ? SORT_KEY_LAST : dup_score_key(v.score[i], !v.is_paired[i]);
+    if (v.paired && i < v.n_tmpl) pair_key[i] = v.pair_a[i] == SORT_KEY_LAST ? SORT_KEY_LAST : dup_score_key(v.score[2 * i] + v.score[2 * i + 1], false);
+}
+
+// the next key of a chain of sorts, in the order the last one left
+__global__ void __launch_bounds__(256) k_dup_gather(const uint64_t* src, const uint32_t* idx, int n, uint64_t* out)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n) out[i] = src[idx[i]];
+}
+
+// The verdicts.  keys / idx: the entries after the last sort; second: the pairs' other key (by entry), or null.  The first entry
+// of a run of equal keys is its keeper -- the highest score, then the lowest index -- and among fragments a paired entry where
+// there is one, so every later entry of the run is a duplicate unless it is itself paired (is_paired == null: the pair rule).
+__global__ void __launch_bounds__(256) k_dup_decide(const uint64_t* keys, const uint32_t* idx, const uint64_t* second, int n, const uint8_t* is_paired, uint8_t* dup)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n || keys[i] == SORT_KEY_LAST) return;
+    const uint32_t e = idx[i];
+    const bool head = i == 0 || keys[i] != keys[i - 1] || (second && second[e] != second[idx[i - 1]]);
+    dup[e] = !head && !(is_paired && is_paired[e]) ? 1 : 0;
+}
+
+// (d) one lane per template walks its records again and sets or clears 0x400 in byte 19 of each: a byte store by the only lane that
+// owns the record.  The duplicates are counted on the way.
+__global__ void __launch_bounds__(64) k_dup_flags(DupView v)
+{
+    const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    int n_frag = 0, n_pair = 0;
+    if (t < v.n_tmpl) {
+        const int r0 = v.paired ? 2 * t : t, nr = v.paired && r0 + 1 < v.n_reads ? 2 : 1;
+        n_pair = v.paired ? v.pair_dup[t] : 0;
+        for (int k = 0; k < nr; ++k) n_frag += v.frag_dup[r0 + k];
+        const uint8_t bit = n_pair || n_frag ? 4 : 0;
+        int64_t o = v.bam_off[r0];
+        const int64_t hi = v.bam_off[r0 + nr];
+        while (hi - o >= BAMSORT_MIN_REC) {                              // (the walk of k_dup_entries has passed)
+            const int64_t size = 4 + (int64_t)(int32_t)bamsort_ld32(v.bam + o);
+            if (size < BAMSORT_MIN_REC || size > hi - o) break;
+            const uint8_t was = v.bam[o + 19], now = (uint8_t)((was & ~4) | bit);
+            if (now != was) v.bam[o + 19] = now;
+            o += size;
+        }
+    }
+    dup_wave_add(n_frag, &v.cnt[DUP_CNT_UNPAIRED_DUP]);
+    dup_wave_add(n_pair, &v.cnt[DUP_CNT_PAIR_DUP]);
+}
+
+void launch_dup_entries(hipStream_t st, const DupView& v)
+{
+    hipLaunchKernelGGL(k_dup_entries, dim3((v.n_tmpl + 63) / 64), dim3(64), 0, st, v);
+}
+void launch_dup_scores(hipStream_t st, const DupView& v, int max_len)
+{
+    if (max_len > 1000) hipLaunchKernelGGL(k_dup_scores<64>, dim3((v.n_reads + 3) / 4), dim3(256), 0, st, v);      // long reads: a wavefront per read
+    else hipLaunchKernelGGL(k_dup_scores<8>, dim3((v.n_reads + 31) / 32), dim3(256), 0, st, v);
+}
+void launch_dup_score_keys(hipStream_t st, const DupView& v, uint64_t* frag_key, uint64_t* pair_key)
+{
+    hipLaunchKernelGGL(k_dup_score_keys, dim3((v.n_reads + 255) / 256), dim3(256), 0, st, v, frag_key, pair_key);
+}
+void launch_dup_gather(hipStream_t st, const uint64_t* src, const uint32_t* idx, int n, uint64_t* out)
+{
+    hipLaunchKernelGGL(k_dup_gather, dim3((n + 255) / 256), dim3(256), 0, st, src, idx, n, out);
+}
+void launch_dup_decide(hipStream_t st, const uint64_t* keys, const uint32_t* idx, const uint64_t* second, int n, const uint8_t* is_paired, uint8_t* dup)
+{
+    hipLaunchKernelGGL(k_dup_decide, dim3((n + 255) / 256), dim3(256), 0, st, keys, idx, second, n, is_paired, dup);
+}
+void launch_dup_flags(hipStream_t st, const DupView& v)
+{
+    hipLaunchKernelGGL(k_dup_flags, dim3((v.n_tmpl + 63) / 64), dim3(64), 0, st, v);
+}
+
 void launch_sort_bits(hipStream_t st, const uint64_t* keys, int64_t n, int32_t* bits)
 {
     if (n <= 0) return;

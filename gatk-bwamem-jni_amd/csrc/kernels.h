@@ -4,6 +4,7 @@
 #include "bwamem_types.h"
 #include "bam_encode.h"
 #include "bam_sort.h"
+#include "bam_dup.h"
 #include "fastq_parse.h"
 
 void launch_build_occ64(hipStream_t st, const uint32_t* bwt, uint64_t n_blocks, uint4* occ);
@@ -73,6 +74,16 @@ void launch_bai_mark(hipStream_t st, const uint64_t* keys, const uint32_t* idx, 
 void launch_bai_chunks(hipStream_t st, const uint64_t* keys, const uint32_t* idx, int n, const int32_t* start, const int64_t* cid, const int64_t* rec_off,
                        const int64_t* member_off, int64_t coffset0, BaiChunk* out);
 void launch_bai_windows(hipStream_t st, const int32_t* win, int n_win, int n_rec, const int64_t* rec_off, const int64_t* member_off, int64_t coffset0, uint64_t* out);
+// Duplicate marking (bam_dup.h): _entries writes the keys, is_paired, the place of QUAL and the counts of every template (v.cnt
+// zeroed by the caller); _scores the reads' scores (max_len: the longest QUAL, v.cnt[DUP_CNT_MAX_LEN]); _score_keys the first sort
+// keys.  Between the sorts of a chain _gather takes the next key in the order of the last; after the last _decide writes the
+// verdicts (dup zeroed by the caller), and _flags rewrites byte 19 of every record and counts the duplicates.
+void launch_dup_entries(hipStream_t st, const DupView& v);
+void launch_dup_scores(hipStream_t st, const DupView& v, int max_len);
+void launch_dup_score_keys(hipStream_t st, const DupView& v, uint64_t* frag_key, uint64_t* pair_key);
+void launch_dup_gather(hipStream_t st, const uint64_t* src, const uint32_t* idx, int n, uint64_t* out);
+void launch_dup_decide(hipStream_t st, const uint64_t* keys, const uint32_t* idx, const uint64_t* second, int n, const uint8_t* is_paired, uint8_t* dup);
+void launch_dup_flags(hipStream_t st, const DupView& v);
 
 // paired-end path (k_pe.hip)
 void launch_pestat_cand(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv, int8_t* cand_dir, int64_t* cand_is);

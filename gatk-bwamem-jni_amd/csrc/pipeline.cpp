@@ -349,6 +349,8 @@ struct OutSink {
 struct BgzfBufs { DevBuf slots, sizes, off, scan_tmp, tokens, out; size_t bytes = 0; };
 // the two sides of the radix sort (bam_sort.h) and its histograms
 struct SortBufs { DevBuf keys[2], idx[2], hist, hist_off, scan_tmp, bits; };
+// duplicate marking (bam_dup.h): the entries of every read and template, their first sort keys, the verdicts
+struct DupBufs { DevBuf frag_end, pair_a, pair_b, qual_off, l_seq, is_paired, score, frag_k1, pair_k1, frag_dup, pair_dup, cnt, bits; };
 
 struct bwamem_batch_s {
     bwaidx_s* idx = nullptr;
@@ -372,6 +374,7 @@ struct bwamem_batch_s {
     size_t bam_n_rec = 0;                            // records of the sorted stream
     DevBuf bam2, rec_cnt, rec_first, rec_src, rec_size, rec_psize, rec_dst, rec_scan_tmp;
     SortBufs srt;
+    DupBufs dup;                                     // bwamem_hip_batch_mark_duplicates
     DevBuf bai_win_base, bai_win, bai_winv, bai_cnt, bai_start, bai_cid, bai_chunks;   // the index (bwamem_hip_batch_index_bam)
     // what the records take from outside the response: base qualities laid out like d_raw (bwamem_hip_batch_set_qualities, or the
     // FASTQ text), names of the batch's own (bwamem_hip_batch_upload_fastq) and the read group (bwamem_hip_batch_set_read_group)
@@ -2085,18 +2088,21 @@ static bool sort_ensure(SortBufs& s, int64_t n)
     return s.keys[0].ensure((size_t)n * 8) && s.keys[1].ensure((size_t)n * 8) && s.idx[0].ensure((size_t)n * 4) && s.idx[1].ensure((size_t)n * 4)
         && s.hist.ensure(nh * 4) && s.hist_off.ensure((nh + 1) * 8) && s.scan_tmp.ensure(scan_tmp_bytes((int64_t)nh + 1)) && s.bits.ensure(SORT_BITS_N * 4);
 }
-// The passes over the bytes named by `live` of the n keys in s.keys[0] (sort_ensure'd), the indices starting as the identity:
-// *side = the side of s that holds the sorted keys and the permutation.  No host wait.
-static bool sort_pairs(Workspace& ws, SortBufs& s, int64_t n, uint32_t live, int* side)
+// The passes over the bytes named by `live` of the n keys in s.keys[0] (sort_ensure'd; keys0: the keys are read from there
+// instead), the indices starting as the identity: *side = the side of s that holds the sorted keys and the permutation.  chained:
+// the keys and the indices are those of side *side, as an earlier call or a gather left them, and nothing runs when nothing
+// varies.  No host wait.
+static bool sort_pairs(Workspace& ws, SortBufs& s, int64_t n, uint32_t live, int* side, const uint64_t* keys0 = nullptr, bool chained = false)
 {
-    if (!(live & 0xff)) live = 1;                                      // nothing varies: one pass still writes the identity
-    int cur = 0;
-    bool first = true;
+    if (!chained && !(live & 0xff)) live = 1;                          // nothing varies: one pass still writes the identity
+    int cur = chained ? *side : 0;
+    bool first = !chained;
     for (int byte = 0; byte < 8; ++byte) {
         if (!(live >> byte & 1)) continue;
-        TIMED(ws, K_OTHER, launch_sort_hist(ws.stream, s.keys[cur].as<uint64_t>(), n, byte, s.hist.as<int32_t>()));
+        const uint64_t* in = first && keys0 ? keys0 : s.keys[cur].as<uint64_t>();
+        TIMED(ws, K_OTHER, launch_sort_hist(ws.stream, in, n, byte, s.hist.as<int32_t>()));
         launch_scan(ws.stream, s.hist.as<int32_t>(), s.hist_off.as<int64_t>(), (int)(SORT_RADIX * sort_n_tiles(n)), s.scan_tmp.as<int64_t>());
-        TIMED(ws, K_OTHER, launch_sort_scatter(ws.stream, s.keys[cur].as<uint64_t>(), first ? nullptr : s.idx[cur].as<uint32_t>(), n, byte, s.hist_off.as<int64_t>(),
+        TIMED(ws, K_OTHER, launch_sort_scatter(ws.stream, in, first ? nullptr : s.idx[cur].as<uint32_t>(), n, byte, s.hist_off.as<int64_t>(),
                                                s.keys[cur ^ 1].as<uint64_t>(), s.idx[cur ^ 1].as<uint32_t>()));
         cur ^= 1; first = false;
     }
@@ -2187,6 +2193,132 @@ int bwamem_hip_sort_pairs_device(bwaidx_t* idx, const uint64_t* keys, size_t n, 
             HIP_OK(hipStreamSynchronize(ws.stream));
             timed_collect(ws);
             return true;
+        };
+        return run() ? 0 : -1;
+    });
+}
+
+// ---- duplicates marked between the encoder and the sort (bam_dup.h; kernels next to the sort's)
+// One chain of stable sorts over n entries: by k1 (the score key), then by every key of `later` in turn (bits: the OR / AND words of
+// each, DUP_BITS_*).  Only the last sort has to put the absent entries behind the others.  *side: where the result is.
+static bool dup_sort_chain(Workspace& ws, SortBufs& s, int64_t n, const uint64_t* k1, const int32_t* bits1, const uint64_t* const* later, const int32_t* const* bits_later,
+                           int n_later, int* side)
+{
+    const uint32_t live1 = dup_live_bytes_inner(bits1);
+    bool started = false;
+    *side = 0;
+    if (live1) { if (!sort_pairs(ws, s, n, live1, side, k1)) return false; started = true; }
+    for (int k = 0; k < n_later; ++k) {
+        const uint32_t live = k + 1 < n_later ? dup_live_bytes_inner(bits_later[k]) : sort_live_bytes(bits_later[k]);
+        if (!started) { if (!sort_pairs(ws, s, n, live, side, later[k])) return false; started = true; continue; }
+        if (!live && k + 1 < n_later) continue;                        // (the last key is gathered in any case: the verdicts read it)
+        TIMED(ws, K_OTHER, launch_dup_gather(ws.stream, later[k], s.idx[*side].as<uint32_t>(), (int)n, s.keys[*side].as<uint64_t>()));
+        if (!sort_pairs(ws, s, n, live, side, nullptr, true)) return false;
+    }
+    return true;
+}
+
+// The records at d_bam (n reads, grouped by read: d_off), marked in place.  The device of ix is current and its lock held.  Three
+// host waits: the walk's errors and the longest read, the OR / AND words of the keys, the counts.  Nothing is stored unless the walk
+// succeeded.
+static bool mark_dup_device(bwaidx_s* ix, uint8_t* d_bam, const int64_t* d_off, size_t n, int paired, DupBufs& d, SortBufs& s, bwamem_dup_counts_t* counts)
+{
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    if (n >= 0x7fffffffu) { fprintf(stderr, "[bwamem_hip] mark_duplicates: too many reads\n"); return false; }
+    const size_t nt = (size_t)dup_templates((int)n, paired);
+    if (!(d.frag_end.ensure(n * 8) && d.pair_a.ensure(nt * 8) && d.pair_b.ensure(nt * 8) && d.qual_off.ensure(n * 8) && d.l_seq.ensure(n * 4) && d.is_paired.ensure(n)
+          && d.score.ensure(n * 4) && d.frag_k1.ensure(n * 8) && d.pair_k1.ensure(nt * 8) && d.frag_dup.ensure(n) && d.pair_dup.ensure(nt) && d.cnt.ensure(DUP_CNT_N * 4)
+          && d.bits.ensure(DUP_BITS_SETS * SORT_BITS_N * 4) && sort_ensure(s, (int64_t)n))) return false;
+    HIP_OK(hipMemsetAsync(d.cnt.p, 0, DUP_CNT_N * 4, ws.stream));
+    HIP_OK(hipMemsetAsync(d.bits.p, 0, DUP_BITS_SETS * SORT_BITS_N * 4, ws.stream));
+    HIP_OK(hipMemsetAsync(d.frag_dup.p, 0, n, ws.stream));
+    HIP_OK(hipMemsetAsync(d.pair_dup.p, 0, nt, ws.stream));
+    DupView v; memset(&v, 0, sizeof v);
+    v.bam = d_bam; v.bam_off = d_off; v.n_reads = (int32_t)n; v.n_tmpl = (int32_t)nt; v.paired = paired ? 1 : 0;
+    v.frag_end = d.frag_end.as<uint64_t>(); v.pair_a = d.pair_a.as<uint64_t>(); v.pair_b = d.pair_b.as<uint64_t>(); v.qual_off = d.qual_off.as<int64_t>();
+    v.l_seq = d.l_seq.as<int32_t>(); v.is_paired = d.is_paired.as<uint8_t>(); v.score = d.score.as<int32_t>(); v.frag_dup = d.frag_dup.as<uint8_t>();
+    v.pair_dup = d.pair_dup.as<uint8_t>(); v.cnt = d.cnt.as<int32_t>();
+    int32_t* const dbits = d.bits.as<int32_t>();
+    TIMED(ws, K_OTHER, launch_dup_entries(ws.stream, v));
+    int32_t cnt[DUP_CNT_N];
+    HIP_OK(hipMemcpyAsync(cnt, d.cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 1: the errors and the longest read
+    if (cnt[DUP_CNT_ERR] & BAMDUP_ERR_KEY) { fprintf(stderr, "[bwamem_hip] mark_duplicates: a record's contig or unclipped position does not fit the key\n"); return false; }
+    if (cnt[DUP_CNT_ERR]) { fprintf(stderr, "[bwamem_hip] mark_duplicates: the records do not chain, or a read has two primary records (flags %d)\n", cnt[DUP_CNT_ERR]); return false; }
+    TIMED(ws, K_OTHER, launch_dup_scores(ws.stream, v, cnt[DUP_CNT_MAX_LEN]));
+    TIMED(ws, K_OTHER, launch_dup_score_keys(ws.stream, v, d.frag_k1.as<uint64_t>(), d.pair_k1.as<uint64_t>()));
+    TIMED(ws, K_OTHER, launch_sort_bits(ws.stream, v.frag_end, (int64_t)n, dbits + DUP_BITS_FRAG_END * SORT_BITS_N));
+    TIMED(ws, K_OTHER, launch_sort_bits(ws.stream, d.frag_k1.as<uint64_t>(), (int64_t)n, dbits + DUP_BITS_FRAG_SCORE * SORT_BITS_N));
+    if (paired) {
+        TIMED(ws, K_OTHER, launch_sort_bits(ws.stream, v.pair_a, (int64_t)nt, dbits + DUP_BITS_PAIR_A * SORT_BITS_N));
+        TIMED(ws, K_OTHER, launch_sort_bits(ws.stream, v.pair_b, (int64_t)nt, dbits + DUP_BITS_PAIR_B * SORT_BITS_N));
+        TIMED(ws, K_OTHER, launch_sort_bits(ws.stream, d.pair_k1.as<uint64_t>(), (int64_t)nt, dbits + DUP_BITS_PAIR_SCORE * SORT_BITS_N));
+    }
+    int32_t bits[DUP_BITS_SETS][SORT_BITS_N];
+    HIP_OK(hipMemcpyAsync(bits, d.bits.p, sizeof bits, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 2: which bytes of the keys vary
+    int side = 0;
+    if (bits[DUP_BITS_FRAG_END][SORT_BITS_HAS_OTHER]) {
+        const uint64_t* later[1] = { v.frag_end }; const int32_t* lb[1] = { bits[DUP_BITS_FRAG_END] };
+        if (!dup_sort_chain(ws, s, (int64_t)n, d.frag_k1.as<uint64_t>(), bits[DUP_BITS_FRAG_SCORE], later, lb, 1, &side)) return false;
+        TIMED(ws, K_OTHER, launch_dup_decide(ws.stream, s.keys[side].as<uint64_t>(), s.idx[side].as<uint32_t>(), nullptr, (int)n, v.is_paired, v.frag_dup));
+    }
+    if (paired && bits[DUP_BITS_PAIR_A][SORT_BITS_HAS_OTHER]) {
+        const uint64_t* later[2] = { v.pair_b, v.pair_a }; const int32_t* lb[2] = { bits[DUP_BITS_PAIR_B], bits[DUP_BITS_PAIR_A] };
+        if (!dup_sort_chain(ws, s, (int64_t)nt, d.pair_k1.as<uint64_t>(), bits[DUP_BITS_PAIR_SCORE], later, lb, 2, &side)) return false;
+        TIMED(ws, K_OTHER, launch_dup_decide(ws.stream, s.keys[side].as<uint64_t>(), s.idx[side].as<uint32_t>(), v.pair_b, (int)nt, nullptr, v.pair_dup));
+    }
+    TIMED(ws, K_OTHER, launch_dup_flags(ws.stream, v));
+    HIP_OK(hipMemcpyAsync(cnt, d.cnt.p, sizeof cnt, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 3: the counts
+    if (counts) {
+        counts->unpaired_reads_examined = (uint64_t)(uint32_t)cnt[DUP_CNT_UNPAIRED]; counts->read_pairs_examined = (uint64_t)(uint32_t)cnt[DUP_CNT_PAIRS];
+        counts->secondary_or_supplementary = (uint64_t)(uint32_t)cnt[DUP_CNT_SECONDARY]; counts->unmapped_reads = (uint64_t)(uint32_t)cnt[DUP_CNT_UNMAPPED];
+        counts->unpaired_read_duplicates = (uint64_t)(uint32_t)cnt[DUP_CNT_UNPAIRED_DUP]; counts->read_pair_duplicates = (uint64_t)(uint32_t)cnt[DUP_CNT_PAIR_DUP];
+    }
+    return true;
+}
+
+int bwamem_hip_batch_mark_duplicates(bwamem_batch_t* b, int paired, bwamem_dup_counts_t* counts)
+{
+    if (counts) memset(counts, 0, sizeof *counts);
+    return guarded("bwamem_hip_batch_mark_duplicates", -1, [&]() -> int {
+        if (!b || !b->idx) return -1;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+        if (!b->bam_encoded) { fprintf(stderr, "[bwamem_hip] mark_duplicates: the batch holds no encoded records\n"); return -1; }
+        if (b->bam_sorted) { fprintf(stderr, "[bwamem_hip] mark_duplicates: the records are sorted already and no longer grouped by read (mark before bwamem_hip_batch_sort_bam)\n"); return -1; }
+        b->bgzf.bytes = 0;
+        if (b->n_reads == 0 || b->bam_bytes == 0) return 0;
+        const bool ok = mark_dup_device(b->idx, b->bam.as<uint8_t>(), b->bam_off.as<int64_t>(), b->n_reads, paired, b->dup, b->srt, counts);
+        timed_collect(b->idx->ws);
+        return ok ? 0 : -1;
+    });
+}
+
+int bwamem_hip_mark_duplicates_device(bwaidx_t* idx, void* records, size_t nBytes, const int64_t* read_off, size_t nReads, int paired, bwamem_dup_counts_t* counts)
+{
+    if (counts) memset(counts, 0, sizeof *counts);
+    return guarded("bwamem_hip_mark_duplicates_device", -1, [&]() -> int {
+        if (!idx || !read_off || (nBytes && !records) || nReads >= 0x7fffffffu || nBytes >= ((size_t)1 << 40)) return -1;
+        if (read_off[0] != 0 || read_off[nReads] != (int64_t)nBytes) { fprintf(stderr, "[bwamem_hip] mark_duplicates_device: the offsets do not span the records\n"); return -1; }
+        for (size_t i = 0; i < nReads; ++i) if (read_off[i + 1] < read_off[i]) { fprintf(stderr, "[bwamem_hip] mark_duplicates_device: the offsets descend at read %zu\n", i); return -1; }
+        if (nReads == 0 || nBytes == 0) return 0;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (hipSetDevice(idx->device) != hipSuccess) return -1;
+        auto run = [&]() -> bool {
+            Workspace& ws = idx->ws;
+            if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+            DevBuf bam, off; DupBufs d; SortBufs s;
+            if (!bam.ensure(nBytes + 8) || !off.ensure((nReads + 1) * 8)) return false;
+            HIP_OK(hipMemcpyAsync(bam.p, records, nBytes, hipMemcpyHostToDevice, ws.stream));
+            HIP_OK(hipMemcpyAsync(off.p, read_off, (nReads + 1) * 8, hipMemcpyHostToDevice, ws.stream));
+            const bool ok = mark_dup_device(idx, bam.as<uint8_t>(), off.as<int64_t>(), nReads, paired, d, s, counts);
+            if (ok) { HIP_OK(hipMemcpyAsync(records, bam.p, nBytes, hipMemcpyDeviceToHost, ws.stream)); }
+            HIP_OK(hipStreamSynchronize(ws.stream));
+            timed_collect(ws);
+            return ok;
         };
         return run() ? 0 : -1;
     });

@@ -523,12 +523,14 @@ void* bwamem_hip_bam_header_rg(bwaidx_t* idx, int sorted, const char* rg_line, s
 
 namespace {
 
-// An aligned batch to a file, everything on the device: encode (names: the caller's, or null), sort if asked, compress, index if
-// asked (fd_bai >= 0), write.  The header carries rg_line when there is one.  Everything is made before the first byte is written.
-int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off, const char* rg_line, int sort, int fd, int fd_bai,
-                      int write_header)
+// An aligned batch to a file, everything on the device: encode (names: the caller's, or null), mark duplicates if asked (counts: the
+// totals, or null), sort if asked, compress, index if asked (fd_bai >= 0), write.  The header carries rg_line when there is one.
+// Everything is made before the first byte is written.
+int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off, const char* rg_line, int mark_dup,
+                      bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header)
 {
     if (bwamem_hip_batch_encode_bam(b, paired, names, name_off) != 0) return -1;
+    if (mark_dup && bwamem_hip_batch_mark_duplicates(b, paired, counts) != 0) return -1;
     if (sort && bwamem_hip_batch_sort_bam(b) != 0) return -1;
     size_t nh = 0, nzh = 0, nz = 0, nb = 0;
     Freed zh, z, bai;
@@ -554,17 +556,13 @@ int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* 
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-// bwamem_hip_align_to_bam_device with the records coordinate-sorted on the device, and the BAI index into fd_bai when asked for
-int bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
-                                   int fd, int fd_bai, int write_header)
+// the request calls that go through batch_to_bam_file
+int request_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
+                        int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header)
 {
     try {
         if (!idx || !opt || !pSeq || nBytes < 4 || fd < 0) return -1;
-        if (fd_bai >= 0 && !write_header) { fprintf(stderr, "[bwamem_hip] align_to_sorted_bam: an index needs the header in the same file\n"); return -1; }
+        if (fd_bai >= 0 && !(sort && write_header)) { fprintf(stderr, "[bwamem_hip] %s: an index needs %sthe header in the same file\n", what, sort ? "" : "a sorted file with "); return -1; }
         uint32_t n_reads; memcpy(&n_reads, pSeq, 4);
         int32_t flag; memcpy(&flag, (const char*)opt + 60, 4);                  // mem_opt_t.flag (BwaMemAligner.java:75)
         const int paired = (flag & 0x2) != 0;
@@ -577,18 +575,17 @@ int bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const me
         BatchOwner bo{ bwamem_hip_batch_upload(idx, pSeq, nBytes) };
         if (!bo.b) return -1;
         if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
-        return batch_to_bam_file(idx, bo.b, paired, readNames ? blob.data() : nullptr, readNames ? name_off.data() : nullptr, nullptr, 1, fd, fd_bai, write_header);
+        return batch_to_bam_file(idx, bo.b, paired, readNames ? blob.data() : nullptr, readNames ? name_off.data() : nullptr, nullptr, mark_dup, counts, sort, fd, fd_bai,
+                                 write_header);
     } catch (...) { return -1; }
 }
 
-// FASTQ text in, a BAM file out: the text is taken apart on the device (fastq_parse.h), so the records carry the reads' own names and
-// base qualities, and RG:Z when rg_line names a read group
-int bwamem_hip_align_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
-                                  const char* rg_line, int sort, int fd, int fd_bai, int write_header)
+int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
+                      const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header)
 {
     try {
         if (!idx || !opt || fd < 0) return -1;
-        if (fd_bai >= 0 && !(sort && write_header)) { fprintf(stderr, "[bwamem_hip] align_fastq_to_bam: an index needs a sorted file with its header\n"); return -1; }
+        if (fd_bai >= 0 && !(sort && write_header)) { fprintf(stderr, "[bwamem_hip] %s: an index needs a sorted file with its header\n", what); return -1; }
         int32_t flag; memcpy(&flag, (const char*)opt + 60, 4);                  // mem_opt_t.flag (BwaMemAligner.java:75)
         const int paired = (flag & 0x2) != 0;
         int64_t bad = -1;
@@ -596,8 +593,43 @@ int bwamem_hip_align_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem
         if (!bo.b) return -1;
         if (rg_line && bwamem_hip_batch_set_read_group(bo.b, rg_line) != 0) return -1;
         if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
-        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, sort, fd, fd_bai, write_header);
+        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, mark_dup, counts, sort, fd, fd_bai, write_header);
     } catch (...) { return -1; }
+}
+
+}  // namespace
+
+extern "C" {
+
+// bwamem_hip_align_to_bam_device with the records coordinate-sorted on the device, and the BAI index into fd_bai when asked for
+int bwamem_hip_align_to_sorted_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
+                                   int fd, int fd_bai, int write_header)
+{
+    return request_to_bam_file("align_to_sorted_bam", idx, opt, pes, pSeq, nBytes, readNames, 0, nullptr, 1, fd, fd_bai, write_header);
+}
+
+// ... with the duplicates marked on the device between encode and sort (bam_dup.h); sort == 0: response order and the plain header
+int bwamem_hip_align_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes, const char* const* readNames,
+                                   int sort, int fd, int fd_bai, int write_header, bwamem_dup_counts_t* counts)
+{
+    if (counts) memset(counts, 0, sizeof *counts);
+    return request_to_bam_file("align_to_marked_bam", idx, opt, pes, pSeq, nBytes, readNames, 1, counts, sort != 0, fd, fd_bai, write_header);
+}
+
+// FASTQ text in, a BAM file out: the text is taken apart on the device (fastq_parse.h), so the records carry the reads' own names and
+// base qualities, and RG:Z when rg_line names a read group
+int bwamem_hip_align_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
+                                  const char* rg_line, int sort, int fd, int fd_bai, int write_header)
+{
+    return fastq_to_bam_file("align_fastq_to_bam", idx, opt, pes, text1, n1, text2, n2, rg_line, 0, nullptr, sort, fd, fd_bai, write_header);
+}
+
+// ... with the duplicates marked on the device between encode and sort (bam_dup.h)
+int bwamem_hip_align_fastq_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
+                                         const char* rg_line, int sort, int fd, int fd_bai, int write_header, bwamem_dup_counts_t* counts)
+{
+    if (counts) memset(counts, 0, sizeof *counts);
+    return fastq_to_bam_file("align_fastq_to_marked_bam", idx, opt, pes, text1, n1, text2, n2, rg_line, 1, counts, sort, fd, fd_bai, write_header);
 }
 
 }  // extern "C"

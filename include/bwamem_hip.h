@@ -218,6 +218,34 @@ bwamem_batch_t* bwamem_hip_batch_upload_fastq(bwaidx_t* idx, const char* text1, 
 int    bwamem_hip_align_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
                                      const char* rg_line, int sort, int fd, int fd_bai, int write_header);
 
+/* Duplicates marked on the device, before the sort (csrc/bam_dup.h; additive).  Between _encode_bam and _sort_bam the records of a
+ * read are contiguous and the two reads of a pair are neighbours, so marking is a few sorts of 8-byte keys and one flag byte per
+ * record: it changes no record's size, place or sort key, and the sort, the compressor and the index do not know about it.  The
+ * rule -- Picard MarkDuplicates' as documented, one library, no optical duplicates -- is at the top of csrc/bam_dup.h and is defined
+ * on the records alone; parity with Picard's own output is not checked anywhere.  One call is marked within itself: duplicates
+ * across calls are the caller's business, like merging the sorted runs.
+ *   _mark_duplicates   after _encode_bam and before _sort_bam: sets 0x400 on every record of a duplicate template and clears it on
+ *                   every other record (paired: reads 2i and 2i + 1 are a template, as for _encode_bam); counts (or NULL) receives
+ *                   the six totals.  Non-zero with a message, and the records as they were, without encoded records or when the
+ *                   batch is sorted already (the records are then no longer grouped by read).  0 with zero counts on a batch
+ *                   without records.  Discards BGZF members; _encode_bam and a new alignment discard the marks with the records.
+ *   bwamem_hip_mark_duplicates_device   tooling: host records grouped by read (read_off: nReads + 1 ascending offsets, the first
+ *                   0 and the last nBytes) are uploaded, marked by the same kernels and handed back in place; idx selects the
+ *                   device.  0 = ok; non-zero, and the records untouched, when they do not parse.
+ *   bwamem_hip_align_to_marked_bam / bwamem_hip_align_fastq_to_marked_bam   bwamem_hip_align_to_sorted_bam (with `sort`: 0 leaves
+ *                   response order and the plain header) / bwamem_hip_align_fastq_to_bam with _mark_duplicates between encode and
+ *                   sort; fd_bai >= 0 needs sort and write_header. */
+typedef struct {
+    uint64_t unpaired_reads_examined, read_pairs_examined, secondary_or_supplementary, unmapped_reads, unpaired_read_duplicates, read_pair_duplicates;
+} bwamem_dup_counts_t;
+int    bwamem_hip_batch_mark_duplicates(bwamem_batch_t* b, int paired, bwamem_dup_counts_t* counts);
+int    bwamem_hip_mark_duplicates_device(bwaidx_t* idx, void* records, size_t nBytes, const int64_t* read_off, size_t nReads, int paired,
+                                         bwamem_dup_counts_t* counts);
+int    bwamem_hip_align_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* pSeq, size_t nBytes,
+                                      const char* const* readNames, int sort, int fd, int fd_bai, int write_header, bwamem_dup_counts_t* counts);
+int    bwamem_hip_align_fastq_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2,
+                                            size_t n2, const char* rg_line, int sort, int fd, int fd_bai, int write_header, bwamem_dup_counts_t* counts);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
