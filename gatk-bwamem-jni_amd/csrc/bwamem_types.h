@@ -172,5 +172,5 @@ struct TileView {
                                   // heaviest reads start first, so a tile's tail is no longer whichever heavy read happened to be dispatched last
     int32_t ext_hbm;              // k_extend keeps its rows in dp_rows (BWAMEM_HIP_DP_ROWS=hbm: tests)
     int32_t gcigar_hbm_only;      // k_gcigar: every wave-form job through the rows in dp_rows (same switch)
-    int32_t pad_;
+    int32_t seed_no_probe;        // k_seed: 0 = probe the short SMEM candidates before the row walk; 1 = walk every candidate (BWAMEM_HIP_SEED_PROBE=0: tests, A/B timing)
 };

@@ -142,8 +142,27 @@ __global__ void k_encode(uint8_t* seq, int64_t n_bytes)
 // memory system saturated.  The sequence of extensions and candidate decisions of each read is exactly upstream's
 // (bwt_smem1 / bwt_seed_strategy1 / mem_collect_intv); only the order of equal-priority list entries before the final
 // sort differs, which the sort removes.
-enum { S_IDLE = 0, S_NEXT = 1, S_FWD = 2, S_BWD = 3, S_P3 = 4 };
+//
+// One thing is NOT done as upstream does it: the backward phase of bwt_smem1 walks every forward candidate [sx, e_j) to
+// the left row by row until it dies, and most of that work is spent on candidates too short to ever emit.  On a large
+// text a prefix of j bases has distinct sizes up to j ~ log4(text), and a candidate [sx-k, sx+j) lives while j + k stays
+// below about that, so a search right after a mismatch walks a triangle of extensions from which nothing of
+// min_seed_len bases comes out.  Let s_j be the leftmost start at which candidate j still has min_intv occurrences
+// (or stops at an ambiguous base / the read start).  (1) A candidate with e_j - s_j < min_seed_len emits nothing that
+// mem_collect_intv keeps.  (2) Taking it out of the row walk changes no other emission: in a row where it survives or
+// dies first it only silences shorter candidates dying there, which are shorter than it is in that row, hence below
+// min_seed_len; a candidate it shadows (or is shadowed by) through the equal-size rule has the same occurrences from
+// that row on, hence the same s and is as mute; `any` / `last_start` only ever decide within one row.  (3) A longer
+// string has no more occurrences than its prefix, so s_j' >= s_j for j' > j: once j has died at s, every j' with
+// e_j' - s < min_seed_len is out without an extension.  So the short candidates (e_j - sx < min_seed_len) are probed one
+// at a time, shortest first, each a plain backward walk of one interval in registers (S_PRB0 reads it from the stack,
+// S_PRB goes on).  A probe that dies at s prunes itself and everything up to e < s + min_seed_len; a probe that is alive
+// at min_seed_len bases ends the probing, and the row walk runs as upstream's over that candidate and the longer ones.
+// `cmask` has bit e_j - sx set for every candidate pushed with e_j - sx < 32 (ends are distinct within a search), so the
+// stack index of the next candidate is a popcount; probing is on for min_seed_len <= 32.
+enum { S_IDLE = 0, S_NEXT = 1, S_FWD = 2, S_P3 = 3, S_BWD = 4, S_PRB0 = 5, S_PRB = 6 };      // (the states that walk to the left are the last three)
 #define SEED_EL_CAP 4
+DEV uint32_t low_bits(int n) { return n <= 0 ? 0u : n >= 32 ? ~0u : (1u << n) - 1u; }
 
 template <bool LDSQ>
 __global__ void __launch_bounds__(64) k_seed(DevIndex ix, MemOpt opt, TileView tv, int K, int refill_min, int narrow)
@@ -161,9 +180,13 @@ __global__ void __launch_bounds__(64) k_seed(DevIndex ix, MemOpt opt, TileView t
     const int min_seed_len = opt.min_seed_len;
     const int split_len = (int)(opt.min_seed_len * opt.split_factor + .499);
     const uint64_t max_intv3 = (uint64_t)(int64_t)(int)opt.max_mem_intv;
+    const bool probe = !tv.seed_no_probe && min_seed_len <= 32;
+    const uint32_t short_mask = low_bits(min_seed_len);            // cmask bits of the candidates with end - sx < min_seed_len
 
     int st = S_IDLE, r = 0, len = 0, pass = 1, x = 0, sx = 0, i = 0, k2 = 0, old_n = 0, mem_n = 0;
     int nf = 0, lo = 0, rd = 0, wr = 0, c = -1, ret = 0, end = 0, n_el = 0;
+    uint32_t cmask = 0;
+    int c0 = 0;                                                     // the base in front of sx, where every probe and the row walk start
     uint64_t min_intv = 1, last_start = 0, last_sz = 0, ik0 = 0, ik1 = 0, iks = 0;
     bool any = false, ovf = false, exhausted = false, el_ok = true;
     const uint8_t* qg = tv.seq;
@@ -183,8 +206,11 @@ __global__ void __launch_bounds__(64) k_seed(DevIndex ix, MemOpt opt, TileView t
 #define QAT(p) (LDSQ ? (int)(sq[((p) >> 3) * 64] >> (((p) & 7) << 2) & 15u) : qat_g(p))
 #define FINISH() do { fin = true; st = S_IDLE; } while (0)       // the read's result is stored once, at the end of the iteration
 #define MEM_PUSH(X0, SZ, INFO) do { if (mem_n >= tv.intv_cap) ovf = true; else { Intv v_; v_.x0 = (X0); v_.x1 = 0; v_.size = (SZ); v_.info = (INFO); mem[mem_n++] = v_; } } while (0)
-#define PUSH_IK() do { if (V.push(nf, ik0, iks, end)) ++nf; else ovf = true; } while (0)
-#define BEGIN_BWD() do { ret = end; lo = 0; rd = wr = nf - 1; i = sx - 1; c = i >= 0 ? QAT(i) : 4; c = c < 4 ? c : -1; st = S_BWD; } while (0)
+#define PUSH_IK() do { if (V.push(nf, ik0, iks, end)) { ++nf; if (end - sx < 32) cmask |= 1u << (end - sx); } else ovf = true; } while (0)
+#define END_SEARCH() do { if (pass == 1) x = ret; else ++k2; st = S_NEXT; } while (0)
+// no base in front of sx: every candidate dies in the first row and only the longest can emit.  Otherwise choose what to probe (`sel`).
+#define BEGIN_BWD() do { ret = end; i = sx - 1; c = i >= 0 ? QAT(i) : 4; c = c < 4 ? c : -1; c0 = c; \
+                         if (c < 0 || !probe) { lo = c < 0 ? nf - 1 : 0; rd = wr = nf - 1; st = S_BWD; } else { sel = true; gone = 0; } } while (0)
 
     for (;;) {
         bool fin = false;
@@ -274,35 +300,44 @@ __global__ void __launch_bounds__(64) k_seed(DevIndex ix, MemOpt opt, TileView t
                 ik0 = lb + 1; iks = lb1 - lb; ik1 = lc + 1;
                 sx = nx; i = sx + 1;
                 if (p3) st = S_P3;
-                else { min_intv = nmin; end = sx + 1; nf = 0; any = false; st = S_FWD; }
+                else { min_intv = nmin; end = sx + 1; nf = 0; cmask = 0; any = false; st = S_FWD; }
             }
         }
 
         // ---- what this lane extends in this iteration
         bool need = false, bw = false, back = false;
         int rc = 0, pend = 0;
-        uint64_t r0 = 0, r1 = 0, rs = 0;
+        uint64_t r0 = ik0, r1 = ik1, rs = iks;                      // the running interval, unless a stack entry is read below
         bool fwd_end = false;                                       // forward phase stopped by the read's end or an ambiguous base
         if (st == S_FWD || st == S_P3) {
             const int cq = i < len ? QAT(i) : 4;
-            if (cq < 4) { need = true; rc = 3 - cq; r0 = ik0; r1 = ik1; rs = iks; }
+            if (cq < 4) { need = true; rc = 3 - cq; }
             else if (st == S_FWD) fwd_end = true;
             else { x = i < len ? i + 1 : len; st = S_NEXT; }        // bwt_seed_strategy1 found nothing from sx
         }
-        if (st == S_BWD) {
-            V.get(rd, nf, r0, rs, pend);
-            bw = true;
+        if (st == S_BWD || st == S_PRB0) {                          // a candidate of the row, or the one a probe starts from (c >= 0 then)
+            V.get(st == S_BWD ? rd : lo, nf, r0, rs, pend);
+            bw = st == S_BWD;
             if (c >= 0) { need = true; back = true; rc = c; }
         }
+        if (st == S_PRB) { need = true; back = true; rc = c; }
+        // the base the next row, or the probe's next step, extends by: asked for here, so that it arrives while the gathers are under way
+        int cn = 4;
+        if (st >= S_BWD) cn = i > 0 ? QAT(i - 1) : 4;
+        cn = cn < 4 ? cn : -1;
+        bool sel = false;                                           // choose the next candidate to probe, or start the row walk
+        bool walk = false;                                          // ... no more probes: the row walk from lo as it is
+        uint32_t gone = 0;                                          // ... else: cmask bits of the candidates pruned so far
 
         // ---- one interval extension per lane, issued by the whole wave together
         uint64_t o0 = 0, o1 = 0, os = 0, em0 = 0, ems = 0, emi = 0;
-        bool emit = false;
+        bool emit = false, adv = false;                             // adv: the running interval becomes the extended one
         if (need) { extend_sm(ix, r0, r1, rs, rc, back, o0, o1, os); ++n_ext; }
+        const bool few = os < min_intv;
 
         // ---- consume the result
         if (bw) {                                                   // backward phase: candidate rd of the row for position i
-            if (!need || os < min_intv) {                           // cannot be extended to i: a match starts at i + 1
+            if (!need || few) {                           // cannot be extended to i: a match starts at i + 1
                 if (wr == nf - 1 && (!any || (uint64_t)(i + 1) < last_start)) {
                     any = true; last_start = (uint64_t)(i + 1);
                     if (pend - (i + 1) >= min_seed_len) {
@@ -321,20 +356,41 @@ __global__ void __launch_bounds__(64) k_seed(DevIndex ix, MemOpt opt, TileView t
             }
             --rd;
             if (rd < lo) {                                          // row complete
-                if (wr == nf - 1) { if (pass == 1) x = ret; else ++k2; st = S_NEXT; }
-                else { lo = wr + 1; rd = wr = nf - 1; --i; c = i >= 0 ? QAT(i) : 4; c = c < 4 ? c : -1; }
+                if (wr == nf - 1) END_SEARCH();
+                else {                                              // (a row without a base: only the longest survivor can emit)
+                    const int nlo = wr + 1;
+                    rd = wr = nf - 1; --i; c = cn;
+                    lo = c < 0 ? nf - 1 : nlo;
+                }
             }
         } else if (st == S_FWD && (need || fwd_end)) {              // upstream pushes the interval whenever its size is about to change
             const bool push = fwd_end || os != iks;
-            const bool stop = fwd_end || (push && os < min_intv);
+            const bool stop = fwd_end || (push && few);
             if (push) PUSH_IK();
             if (stop) BEGIN_BWD();                                  // (moot if the push overflowed: the read is abandoned below)
-            else { ik0 = o0; ik1 = o1; iks = os; end = i + 1; ++i; }
+            else { adv = true; end = i + 1; ++i; }
+        } else if (st >= S_PRB0) {                                  // probe of candidate lo: [i, end) has os occurrences
+            if (st == S_PRB0) { end = pend; st = S_PRB; }
+            bool dead = few;
+            if (!dead && end - i >= min_seed_len) { sel = true; walk = true; }   // it may emit: rows from the start, over lo and the longer ones
+            else {
+                if (!dead) { adv = true; --i; c = cn; dead = c < 0; }
+                // its last live start is s = i + 1: the candidates with end - s < min_seed_len go (0 <= sx - s <= min_seed_len - 2)
+                if (dead) { sel = true; gone = ~0u >> (sx - i - 1 + 32 - min_seed_len); }
+            }
         } else if (need) {                                          // S_P3
             if (os < max_intv3 && i - sx >= min_seed_len) {
                 if (os > 0) { emit = true; em0 = o0; ems = os; emi = (uint64_t)sx << 32 | (uint32_t)(i + 1); }
                 x = i + 1; st = S_NEXT;
-            } else { ik0 = o0; ik1 = o1; iks = os; ++i; }
+            } else { adv = true; ++i; }
+        }
+        if (adv) { ik0 = o0; ik1 = o1; iks = os; }
+        if (sel) {                                                  // (sx > 0 and the base in front of sx is not ambiguous: BEGIN_BWD)
+            if (!walk) lo = __popc(cmask & gone);
+            i = sx - 1; c = c0;
+            if (!walk && (cmask & ~gone & short_mask)) st = S_PRB0;      // the shortest candidate left is a short one: probe it
+            else if (lo >= nf) END_SEARCH();                        // nothing left that could emit
+            else { rd = wr = nf - 1; st = S_BWD; }
         }
         if (emit) MEM_PUSH(em0, ems, emi);                          // one store site for both kinds of match
         if (ovf) FINISH();
@@ -347,6 +403,7 @@ __global__ void __launch_bounds__(64) k_seed(DevIndex ix, MemOpt opt, TileView t
 #undef FINISH
 #undef MEM_PUSH
 #undef PUSH_IK
+#undef END_SEARCH
 #undef BEGIN_BWD
     // one counter atomic per wave
     unsigned long long tot = n_ext;
@@ -685,8 +742,10 @@ void launch_seed(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const Ti
     const int groups = (tv.n_reads + 63) / 64;
     int grid = groups < n_cu * wpc ? groups : n_cu * wpc;
     if (tv.smem_groups > 0 && grid > tv.smem_groups) grid = tv.smem_groups;
-    if (ldsq) hipLaunchKernelGGL(k_seed<true>, dim3(grid), dim3(64), lds, st, ix, opt, tv, K, refill_min, narrow);
-    else hipLaunchKernelGGL(k_seed<false>, dim3(grid), dim3(64), lds, st, ix, opt, tv, K, refill_min, narrow);
+    TileView tvs = tv;
+    { const char* e = getenv("BWAMEM_HIP_SEED_PROBE"); if (e && e[0] == '0' && !e[1]) tvs.seed_no_probe = 1; }   // tests, A/B timing: walk every candidate
+    if (ldsq) hipLaunchKernelGGL(k_seed<true>, dim3(grid), dim3(64), lds, st, ix, opt, tvs, K, refill_min, narrow);
+    else hipLaunchKernelGGL(k_seed<false>, dim3(grid), dim3(64), lds, st, ix, opt, tvs, K, refill_min, narrow);
     hipLaunchKernelGGL(k_seed_fin, dim3((tv.n_reads + 255) / 256), dim3(256), 0, st, opt, tv);
 }
 size_t scan_tmp_bytes(int64_t n) { return (size_t)((n + 4095) / 4096 + 2) * 8; }
