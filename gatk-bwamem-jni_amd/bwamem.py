@@ -78,6 +78,10 @@ _lib.bwamem_hip_align_to_marked_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, 
                                                 ctypes.POINTER(_DupCounts)]
 _lib.bwamem_hip_align_fastq_to_marked_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_int, ctypes.c_int, ctypes.POINTER(_DupCounts)]
+_lib.bwamem_hip_align_fastq_gz_to_marked_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_DupCounts)]
+_lib.bwamem_hip_bgzf_inflate_device.restype = _vp
+_lib.bwamem_hip_bgzf_inflate_device.argtypes = [_vp, ctypes.c_char_p, _sz, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int64)]
 
 
 def _taken(p, n):
@@ -502,7 +506,9 @@ class BwaMemAligner:
         return counts.as_dict() if mark_duplicates else None
 
     def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False):
-        """Additive: FASTQ in, a BAM file out.  fastq1 / fastq2: FASTQ text (bytes), or the path of an uncompressed FASTQ file (str);
+        """Additive: FASTQ in, a BAM file out.  fastq1 / fastq2: FASTQ text (bytes), or the path of a FASTQ file (str); bytes or a
+        file that begin with 1f 8b are compressed FASTQ and are handed over as they are: BGZF (bgzip) is inflated on the device, plain
+        gzip on the host (csrc/bgzf_inflate.h);
         with fastq2 the two hold the first and second reads of the pairs, without it fastq1 holds single-end reads or -- after
         alignPairs() -- interleaved pairs.  The text is taken apart on the device: the records carry the reads' names and base
         qualities, and RG:Z:<ID> when read_group (an "@RG\\tID:..." header line) is given.  sort / index_path as alignSeqsToBam.
@@ -527,7 +533,12 @@ class BwaMemAligner:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
             try:
-                if mark_duplicates:
+                if any(t is not None and t[:2] == b"\x1f\x8b" for t in (t1, t2)):
+                    if not all(t is None or t[:2] == b"\x1f\x8b" for t in (t1, t2)):
+                        raise ValueError("fastq1 and fastq2 must both be compressed or both be text")
+                    rc = _lib.bwamem_hip_align_fastq_gz_to_marked_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, rg, 1 if sort else 0, fd, fd_bai, 1,
+                                                                      1 if mark_duplicates else 0, ctypes.byref(counts))
+                elif mark_duplicates:
                     rc = _lib.bwamem_hip_align_fastq_to_marked_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, rg, 1 if sort else 0, fd, fd_bai, 1,
                                                                    ctypes.byref(counts))
                 else:
@@ -541,6 +552,23 @@ class BwaMemAligner:
         if rc != 0:
             raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s (malformed FASTQ, or a device error)" % (self.index.indexImageFile, path))
         return counts.as_dict() if mark_duplicates else None
+
+    def inflateBgzf(self, data):
+        """Additive, for tooling: the bytes of a BGZF stream inflated on the device (the counterpart of the device compressor).  Raises
+        ValueError naming the smallest member that does not inflate."""
+        data = bytes(data)
+        sz, bad = ctypes.c_size_t(), ctypes.c_int64(-1)
+        idx = self.index.refIndex()
+        try:
+            p = _lib.bwamem_hip_bgzf_inflate_device(idx, data, len(data), ctypes.byref(sz), ctypes.byref(bad))
+        finally:
+            self.index.deRefIndex()
+        if not p:
+            raise ValueError("not a BGZF stream that inflates (member %d)" % bad.value)
+        try:
+            return ctypes.string_at(p, sz.value)
+        finally:
+            _lib.jnibwa_free(p)
 
     def alignSeqs(self, sequences, func=lambda s: s):
         """BwaMemAligner.java:192-310: one list of BwaMemAlignment per input sequence"""

@@ -18,7 +18,9 @@
 //               and their trimmed names must be equal.  One interleaved text: bwamem_hip_batch_encode_bam(paired = 1) makes the
 //               same name check.  bad_record counts reads of the batch: the record's index in a single text, 2i or 2i + 1 for
 //               two texts, the first read of a pair whose names differ.
-// Compressed FASTQ is out of scope, and so is cutting a file larger than one call (one request under 2 GiB, as everywhere).
+// Compressed FASTQ comes in through bwamem_hip_batch_upload_fastq_gz: BGZF members are inflated on the device into the place the
+// text would have been copied to (bgzf_inflate.h), and everything below runs on that text unchanged.  Cutting a file larger than
+// one call is out of scope (one request under 2 GiB of text, as everywhere).
 //
 // The line index.  A text of n bytes has a newline at p when text[p] == '\n', and one more at p == n when n > 0 and the last
 // byte is no '\n' (the last line lacks its newline).  Line k (from 0) starts at start[k] and ends before start[k + 1] - 1, with

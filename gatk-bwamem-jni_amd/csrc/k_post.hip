@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "post_common.h"
 #include "bgzf_deflate.h"
+#include "bgzf_inflate.h"
 #include "bam_sort.h"
 #include "fastq_parse.h"
 
@@ -661,6 +662,280 @@ __global__ void __launch_bounds__(256) k_bgzf_gather(const uint8_t* slots, const
     if (tid < tail) d[lead + 4 * nw + tid] = s[lead + 4 * nw + tid];
 }
 
+// ------------------------------------------------------------------ BGZF members inflated on the device (bgzf_inflate.h)
+// One wavefront per member and 8 KB of LDS, so that many members are in flight per CU (8 as compiled: the registers bind): symbol
+// decoding is serial per member and the number of members in flight is the throughput.  The member is worked off in turns; the state between turns
+// (bit position, output position, in a block or between blocks) is a few LDS words written by lane 0 only.
+//   stage    all lanes load BGZI_WIN bytes of the deflate area from the 16-byte word holding the current bit into LDS with
+//            16-byte loads; bytes outside the area are zeroed, so the decoding lane never waits on a global load and never sees a
+//            byte that is not the member's.
+//   header   (between blocks) lane 0 reads the block header; a stored block is copied by all lanes; for a dynamic block lane 0
+//            reads the code-length code and the lengths, for a fixed block all lanes write the fixed lengths; lane 0 makes the
+//            count / sorted-symbol arrays and the validity checks; all lanes fill the primary tables by decoding every index.
+//   decode   (in a block) lane 0 decodes up to BGZI_TOK tokens (bgzf_deflate.h's format) and their output positions into LDS,
+//            checking every distance and length against the member's first and last output byte.
+//   output   literals are stored at once; matches in rounds: everything below the lowest unresolved match is final, so every match
+//            whose source ends there can go -- one lane per short match, the whole wavefront for a long one.  A match with
+//            distance < length reads its source modulo the distance, i.e. only bytes that were final before the round.  Output
+//            goes straight to HBM; later rounds read earlier rounds' stores of the same workgroup (same CU) after a
+//            workgroup-scope fence.
+// Then the CRC-32 of the output by all lanes (slices combined as in k_bgzf_deflate) against the trailer.
+struct BgziBits { uint64_t hold; int nbits, wpos; };
+static __device__ inline void bgzi_refill(const uint32_t* win, BgziBits& r)          // at least 33 bits afterwards
+{
+    if (r.nbits <= 32) { r.hold |= (uint64_t)(r.wpos < BGZI_WIN_DW ? win[r.wpos] : 0u) << r.nbits; ++r.wpos; r.nbits += 32; }
+}
+static __device__ inline uint32_t bgzi_take(BgziBits& r, int n)                      // n <= 31
+{
+    const uint32_t v = (uint32_t)r.hold & ((1u << n) - 1u);
+    r.hold >>= n; r.nbits -= n;
+    return v;
+}
+static __device__ inline void bgzi_open(const uint32_t* win, BgziBits& r, int bit)   // the reader at bit `bit` of the window
+{
+    r.hold = 0; r.nbits = 0; r.wpos = bit >> 5;
+    bgzi_refill(win, r); (void)bgzi_take(r, bit & 31); bgzi_refill(win, r);
+}
+#define BGZI_POS(r) (8 * base_off + 32 * (r).wpos - (r).nbits)       // the reader's bit position in the deflate area
+
+__global__ void __launch_bounds__(BGZI_THREADS) k_bgzf_inflate(const uint8_t* comp, const BgzfMember* mem, int n_members, int member0, uint8_t* text, int32_t* err)
+{
+    __shared__ uint32_t s_win[BGZI_WIN_DW], s_tok[BGZI_TOK], s_crc[256];
+    __shared__ uint16_t s_tpos[BGZI_TOK], s_pll[1 << BGZI_LL_PB], s_pd[1 << BGZI_D_PB];
+    __shared__ uint16_t s_symll[288], s_symd[32], s_symcl[DFL_NCL + 1], s_cntll[16], s_cntd[16], s_cntcl[16], s_offs[16];
+    __shared__ uint8_t s_len[288 + 32], s_lencl[DFL_NCL + 1];
+    __shared__ int s_bitpos, s_opos, s_inblock, s_last, s_bad, s_done, s_ntok, s_kind, s_slen, s_ssrc, s_sdst;
+
+    const int lane = (int)threadIdx.x, m = (int)blockIdx.x;
+    if (m >= n_members) return;
+    const BgzfMember M = mem[m];
+    const uint8_t* in = comp + M.coff + M.hlen;                      // the deflate area: dlen bytes
+    const int dlen = M.csize - M.hlen - BGZF_TAIL, isize = M.isize;
+    uint8_t* out = text + M.uoff;
+    for (int k = lane; k < 256; k += BGZI_THREADS) s_crc[k] = bgz_crc_table_entry((uint32_t)k);
+    if (lane == 0) { s_bitpos = 0; s_opos = 0; s_inblock = 0; s_last = 0; s_bad = 0; s_done = 0; s_ntok = 0; s_kind = 0; }
+    __syncthreads();
+    bool bad = dlen < 0 || isize < 0 || isize > BGZI_MAX_ISIZE, done = false;        // (the host's walk has checked these)
+    // every turn consumes at least one bit or ends the member
+    const int64_t max_turns = 8 * (int64_t)(dlen > 0 ? dlen : 0) + 2;
+    for (int64_t turn = 0; turn < max_turns && !bad && !done; ++turn) {
+        const int bitpos = s_bitpos, opos0 = s_opos, inblock = s_inblock, last = s_last;
+        const int byte = bitpos >> 3, base_off = byte - (int)((uintptr_t)(in + byte) & 15);
+        __syncthreads();
+        // ---- stage
+        for (int c = lane; c < BGZI_WIN / 16; c += BGZI_THREADS) {
+            const int off = base_off + 16 * c;
+            uint32_t w[4] = { 0, 0, 0, 0 };
+            if (off + 16 > 0 && off < dlen) {
+                const uint4 v = *(const uint4*)(in + off);
+                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+                if (off < 0 || off + 16 > dlen)
+                    for (int b = 0; b < 16; ++b) if (off + b < 0 || off + b >= dlen) w[b >> 2] &= ~(0xffu << (8 * (b & 3)));
+            }
+            for (int k = 0; k < 4; ++k) s_win[4 * c + k] = w[k];
+        }
+        __syncthreads();
+        if (!inblock) {
+            // ---- header
+            if (lane == 0) {
+                BgziBits r;
+                bgzi_open(s_win, r, bitpos - 8 * base_off);
+                bool fail = false;
+                const int fin = (int)bgzi_take(r, 1), type = (int)bgzi_take(r, 2);
+                s_kind = type; s_last = fin;
+                if (type == 3) fail = true;
+                else if (type == 0) {
+                    (void)bgzi_take(r, r.nbits & 7);
+                    bgzi_refill(s_win, r);
+                    const int len = (int)bgzi_take(r, 16), nlen = (int)bgzi_take(r, 16);
+                    const int src = BGZI_POS(r) >> 3;
+                    if (len != (~nlen & 0xffff) || src + len > dlen || opos0 + len > isize) fail = true;
+                    else {
+                        s_slen = len; s_ssrc = src; s_sdst = opos0; s_opos = opos0 + len; s_bitpos = 8 * (src + len);
+                        if (fin) { if (src + len != dlen || opos0 + len != isize) fail = true; else s_done = 1; }
+                    }
+                } else {
+                    if (type == 2) {
+                        bgzi_refill(s_win, r);
+                        const int hlit = 257 + (int)bgzi_take(r, 5), hdist = 1 + (int)bgzi_take(r, 5), hclen = 4 + (int)bgzi_take(r, 4);
+                        const int total = hlit + hdist;
+                        if (hlit > DFL_NLL || hdist > DFL_ND) fail = true;
+                        for (int i = 0; i < DFL_NCL; ++i) s_lencl[i] = 0;
+                        for (int i = 0; i < hclen; ++i) { bgzi_refill(s_win, r); s_lencl[dfl_cl_order(i)] = (uint8_t)bgzi_take(r, 3); }
+                        if (!fail && !dfl_canonical(s_lencl, DFL_NCL, BGZI_CODES, s_cntcl, s_symcl, s_offs)) fail = true;
+                        int i = 0;
+                        while (!fail && i < total) {                 // at most 316 lengths
+                            bgzi_refill(s_win, r);
+                            const uint32_t e = dfl_decode_walk((uint32_t)r.hold, s_cntcl, s_symcl, DFL_CL_BITS);
+                            if (!e) { fail = true; break; }
+                            (void)bgzi_take(r, (int)(e >> 12));
+                            const int sym = (int)(e & 0xfff);
+                            if (sym < 16) { s_len[i++] = (uint8_t)sym; continue; }
+                            int rep, val = 0;
+                            if (sym == 16) { if (i == 0) { fail = true; break; } val = s_len[i - 1]; rep = 3 + (int)bgzi_take(r, 2); }
+                            else if (sym == 17) rep = 3 + (int)bgzi_take(r, 3);
+                            else rep = 11 + (int)bgzi_take(r, 7);
+                            if (i + rep > total) { fail = true; break; }
+                            for (; rep > 0; --rep) s_len[i++] = (uint8_t)val;
+                        }
+                        if (!fail && s_len[DFL_EOB] == 0) fail = true;
+                        if (!fail) {                                 // the distance lengths to their own place, the rest zero
+                            for (int k = hdist - 1; k >= 0; --k) s_len[288 + k] = s_len[hlit + k];
+                            for (int k = hlit; k < 288; ++k) s_len[k] = 0;
+                            for (int k = 288 + hdist; k < 320; ++k) s_len[k] = 0;
+                        }
+                    }
+                    const int pos = BGZI_POS(r);
+                    if (pos > 8 * dlen) fail = true;
+                    s_bitpos = pos;
+                }
+                if (fail) s_bad = 1;
+            }
+            __syncthreads();
+            const int kind = s_kind;
+            bad = s_bad != 0;
+            if (!bad && kind == 0) {                                 // a stored block: within both areas, checked above
+                const int n = s_slen;
+                const uint8_t* src = in + s_ssrc;
+                uint8_t* dst = out + s_sdst;
+                for (int i = lane; i < n; i += BGZI_THREADS) dst[i] = src[i];
+            }
+            if (!bad && kind == 1) {
+                for (int s = lane; s < 288; s += BGZI_THREADS) s_len[s] = (uint8_t)dfl_fixed_ll_len(s);
+                if (lane < 32) s_len[288 + lane] = 5;
+            }
+            __syncthreads();
+            if (!bad && kind != 0) {
+                if (lane == 0) {
+                    if (dfl_canonical(s_len, 288, BGZI_LENS, s_cntll, s_symll, s_offs) && dfl_canonical(s_len + 288, 32, BGZI_DISTS, s_cntd, s_symd, s_offs)) s_inblock = 1;
+                    else s_bad = 1;
+                }
+                __syncthreads();
+                bad = s_bad != 0;
+                if (!bad) {
+                    for (int e = lane; e < 1 << BGZI_LL_PB; e += BGZI_THREADS) s_pll[e] = (uint16_t)dfl_decode_walk((uint32_t)e, s_cntll, s_symll, BGZI_LL_PB);
+                    for (int e = lane; e < 1 << BGZI_D_PB; e += BGZI_THREADS) s_pd[e] = (uint16_t)dfl_decode_walk((uint32_t)e, s_cntd, s_symd, BGZI_D_PB);
+                }
+            }
+            __syncthreads();
+            done = s_done != 0;
+            continue;
+        }
+        // ---- decode
+        if (lane == 0) {
+            BgziBits r;
+            bgzi_open(s_win, r, bitpos - 8 * base_off);
+            int ntok = 0, opos = opos0;
+            bool fail = false, eob = false;
+            while (ntok < BGZI_TOK && r.wpos + 2 <= BGZI_WIN_DW) {
+                bgzi_refill(s_win, r);
+                uint32_t e = s_pll[(uint32_t)r.hold & ((1u << BGZI_LL_PB) - 1u)];
+                if (!e) e = dfl_decode_walk((uint32_t)r.hold, s_cntll, s_symll, DFL_LL_BITS);
+                if (!e) { fail = true; break; }
+                (void)bgzi_take(r, (int)(e >> 12));
+                const int sym = (int)(e & 0xfff);
+                if (sym < DFL_EOB) {
+                    if (opos >= isize) { fail = true; break; }
+                    s_tok[ntok] = (uint32_t)sym; s_tpos[ntok] = (uint16_t)opos;
+                    ++ntok; ++opos;
+                    continue;
+                }
+                if (sym == DFL_EOB) { eob = true; break; }
+                if (sym >= DFL_NLL) { fail = true; break; }
+                const int len = dfl_len_base(sym) + (int)bgzi_take(r, dfl_len_extra_bits(sym));
+                bgzi_refill(s_win, r);
+                e = s_pd[(uint32_t)r.hold & ((1u << BGZI_D_PB) - 1u)];
+                if (!e) e = dfl_decode_walk((uint32_t)r.hold, s_cntd, s_symd, DFL_LL_BITS);
+                if (!e) { fail = true; break; }
+                (void)bgzi_take(r, (int)(e >> 12));
+                const int dsym = (int)(e & 0xfff);
+                if (dsym >= DFL_ND) { fail = true; break; }
+                const int dist = dfl_dist_base(dsym) + (int)bgzi_take(r, dfl_dist_extra_bits(dsym));
+                if (dist > opos || opos + len > isize) { fail = true; break; }
+                s_tok[ntok] = dfl_tok_match(len, dist); s_tpos[ntok] = (uint16_t)opos;
+                ++ntok; opos += len;
+            }
+            const int pos = BGZI_POS(r);
+            if (pos > 8 * dlen) fail = true;                         // the bits came from beyond the deflate area
+            if (!fail && eob) {
+                s_inblock = 0;
+                if (last) { if (((pos + 7) >> 3) != dlen || opos != isize) fail = true; else s_done = 1; }
+            }
+            s_ntok = ntok; s_opos = opos; s_bitpos = pos;
+            if (fail) s_bad = 1;
+        }
+        __syncthreads();
+        bad = s_bad != 0;
+        done = s_done != 0;
+        if (bad) break;
+        // ---- output
+        const int ntok = s_ntok;
+        uint32_t t[BGZI_TOK / BGZI_THREADS]; int p[BGZI_TOK / BGZI_THREADS]; bool un[BGZI_TOK / BGZI_THREADS];
+#pragma unroll
+        for (int j = 0; j < BGZI_TOK / BGZI_THREADS; ++j) {
+            const int k = lane + BGZI_THREADS * j;
+            t[j] = 0; p[j] = 0; un[j] = false;
+            if (k >= ntok) continue;
+            t[j] = s_tok[k]; p[j] = s_tpos[k];
+            if (t[j] & DFL_TOK_MATCH) un[j] = p[j] + dfl_tok_len(t[j]) <= isize && dfl_tok_dist(t[j]) <= p[j];     // (as the decoding lane checked)
+            else if (p[j] < isize) out[p[j]] = (uint8_t)t[j];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __syncthreads();
+        for (int round = 0; round < BGZI_TOK; ++round) {             // every round resolves the lowest unresolved match at least
+            int f = 0x7fffffff;
+#pragma unroll
+            for (int j = 0; j < BGZI_TOK / BGZI_THREADS; ++j) if (un[j] && p[j] < f) f = p[j];
+            for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(f, o); if (u < f) f = u; }
+            if (f == 0x7fffffff) break;
+#pragma unroll
+            for (int j = 0; j < BGZI_TOK / BGZI_THREADS; ++j) {
+                const int len = dfl_tok_len(t[j]), d = dfl_tok_dist(t[j]);
+                const bool can = un[j] && p[j] - d + (len < d ? len : d) <= f;
+                const bool big = can && len > BGZI_COOP_LEN;
+                unsigned long long mask = __ballot(big);
+                while (mask) {                                       // a long match: the whole wavefront
+                    const int from = __ffsll((long long)mask) - 1;
+                    mask &= mask - 1;
+                    const int bp = __shfl(p[j], from);
+                    const uint32_t bt = __shfl(t[j], from);
+                    const int bl = dfl_tok_len(bt), bd = dfl_tok_dist(bt);
+                    for (int i = lane; i < bl; i += BGZI_THREADS) out[bp + i] = out[bp - bd + (bd >= bl ? i : i % bd)];
+                }
+                if (can && !big) {                                   // a short one: this lane, eight bytes at a time
+                    const uint8_t* src = out + p[j] - d;
+                    uint8_t* dst = out + p[j];
+                    for (int c = 0; c < len; c += 8) {
+                        uint8_t v[8];
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) v[q] = c + q < len ? src[d >= len ? c + q : (c + q) % d] : (uint8_t)0;
+#pragma unroll
+                        for (int q = 0; q < 8; ++q) if (c + q < len) dst[c + q] = v[q];
+                    }
+                }
+                if (can) un[j] = false;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __syncthreads();
+        }
+    }
+    if (!bad && !done) bad = true;
+    // ---- CRC-32 of the output against the trailer
+    if (!bad) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        __syncthreads();
+        const int per = (isize + BGZI_THREADS - 1) / BGZI_THREADS, lo = lane * per < isize ? lane * per : isize, hi = lo + per < isize ? lo + per : isize;
+        uint32_t c = lane == 0 ? 0xffffffffu : 0u;
+        for (int q = lo; q < hi; ++q) c = s_crc[(c ^ out[q]) & 0xff] ^ (c >> 8);
+        uint32_t x = lane == 0 || lo < hi ? bgz_crc_mul(c, bgz_crc_xpow8((uint32_t)(isize - hi))) : 0u;
+        for (int o = 32; o > 0; o >>= 1) x ^= __shfl_xor(x, o);
+        const uint8_t* tr = comp + M.coff + M.csize - BGZF_TAIL;
+        const uint32_t want = (uint32_t)tr[0] | (uint32_t)tr[1] << 8 | (uint32_t)tr[2] << 16 | (uint32_t)tr[3] << 24;
+        if (~x != want) bad = true;
+    }
+    if (bad && lane == 0) atomicMax(err, (int32_t)(BGZI_NO_ERROR - (member0 + m)));
+}
+
 // ------------------------------------------------------------------ stable radix sort of (key, index) pairs (bam_sort.h)
 // the lanes' words of SortBits, OR-ed over the wavefront, then into bits[] by one lane per wavefront (every lane of the
 // workgroup calls this)
@@ -1121,6 +1396,11 @@ void launch_bgzf_deflate(hipStream_t st, const uint8_t* src, int64_t n, int n_bl
 void launch_bgzf_gather(hipStream_t st, const uint8_t* slots, const int32_t* sizes, const int64_t* off, int n_blocks, bool with_eof, uint8_t* out)
 {
     hipLaunchKernelGGL(k_bgzf_gather, dim3(n_blocks + 1), dim3(256), 0, st, slots, sizes, off, n_blocks, with_eof ? 1 : 0, out);
+}
+
+void launch_bgzf_inflate(hipStream_t st, const uint8_t* comp, const BgzfMember* mem, int n_members, int member0, uint8_t* text, int32_t* err)
+{
+    if (n_members > 0) hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)n_members), dim3(BGZI_THREADS), 0, st, comp, mem, n_members, member0, text, err);
 }
 
 void launch_bam_size(hipStream_t st, const BamTile& t)

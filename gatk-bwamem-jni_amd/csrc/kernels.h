@@ -6,6 +6,7 @@
 #include "bam_sort.h"
 #include "bam_dup.h"
 #include "fastq_parse.h"
+#include "bgzf_inflate.h"
 
 void launch_build_occ64(hipStream_t st, const uint32_t* bwt, uint64_t n_blocks, uint4* occ);
 // suffix array at every ix.sa_intv-th rank (lo/hi, (seq_len >> sa_shift) + 1 entries) from the image's sampling; *err: device int, OR-ed on failure
@@ -54,6 +55,10 @@ int bgzf_grid(int n_cu, int64_t n_blocks);
 size_t bgzf_token_bytes(int grid);
 void launch_bgzf_deflate(hipStream_t st, const uint8_t* src, int64_t n, int n_blocks, int grid, uint8_t* slots, int32_t* sizes, uint32_t* tokens);
 void launch_bgzf_gather(hipStream_t st, const uint8_t* slots, const int32_t* sizes, const int64_t* off, int n_blocks, bool with_eof, uint8_t* out);
+// The reverse (bgzf_inflate.h): member m of the table mem[0, n_members) -- comp + coff, csize bytes -- inflated into text + uoff by one
+// wavefront; comp is 16-byte aligned and padded by 16 bytes.  A refused member atomicMax-es BGZI_NO_ERROR - (member0 + m) into
+// err[0] (zeroed by the caller)
+void launch_bgzf_inflate(hipStream_t st, const uint8_t* comp, const BgzfMember* mem, int n_members, int member0, uint8_t* text, int32_t* err);
 // Stable LSD radix sort of n (64-bit key, 32-bit index) pairs (bam_sort.h).  _bits: the OR / AND words of the keys into bits
 // (SORT_BITS_N ints, zeroed by the caller; sort_live_bytes names the passes to run).  One pass over byte `byte`: _hist into hist
 // (256 * sort_n_tiles(n) ints), launch_scan over them, _scatter from (keys, idx) to (keys_out, idx_out); idx == null: the identity.

@@ -1452,6 +1452,7 @@ template <typename R, typename F> static R guarded(const char* what, R fail, F&&
 }
 
 const std::vector<ContigInfo>& bwamem_index_contigs(const bwaidx_t* idx) { return idx->h.contigs; }     // (sam_writer.cpp)
+bool bwamem_gunzip_host(const void* src, size_t n, size_t limit, std::vector<char>& out);               // (sam_writer.cpp: libz at run time)
 
 extern "C" {
 
@@ -1867,12 +1868,27 @@ static bool set_read_group(bwamem_batch_s* b, const char* rg_line)
 // The texts go to HBM as they are; the kernels index their lines, check every record and lay out the payload bwamem_hip_batch_upload
 // would have built, the qualities next to it, and the names.  Two host waits: the line counts, then the totals.  The device of ix
 // is current and its lock held.  *made: the batch, or null with *bad set (malformed input); false: a device error.
-static bool upload_fastq(bwaidx_s* ix, const char* const text[2], const size_t n_text[2], int n_texts, int64_t* bad, bwamem_batch_s** made)
+// A text is either host bytes, copied as they are, or the BGZF members of a compressed stream (bgzf_inflate.h): then the compressed
+// bytes and the member table go up and k_bgzf_inflate writes the text where the copy would have put it.  The inflate adds no wait:
+// its error word is read in wait 1, and a refused member ends the call there (*bad_member: members of the first stream, then of
+// the second).
+struct FastqSource {
+    int n_texts = 1;
+    const char* text[2] = { nullptr, nullptr }; size_t n_text[2] = { 0, 0 };         // the size of a text is known on the host either way
+    const uint8_t* gz[2] = { nullptr, nullptr }; size_t n_gz[2] = { 0, 0 };          // non-null: inflate these members on the device
+    std::vector<BgzfMember> mem[2];
+};
+
+static bool upload_fastq(bwaidx_s* ix, const FastqSource& src, int64_t* bad, int64_t* bad_member, bwamem_batch_s** made)
 {
     Workspace& ws = ix->ws;
     if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
-    *made = nullptr; *bad = -1;
-    DevBuf txt[2], counts[2], base[2], start[2], scan_tmp, len1, l_name, seq_off, name_off, err;
+    *made = nullptr; *bad = -1; *bad_member = -1;
+    const int n_texts = src.n_texts;
+    const size_t* n_text = src.n_text;
+    DevBuf txt[2], counts[2], base[2], start[2], scan_tmp, len1, l_name, seq_off, name_off, err, zc[2], zm[2], zerr;
+    const bool inflate = src.gz[0] || (n_texts == 2 && src.gz[1]);
+    if (inflate) { if (!zerr.ensure(64)) return false; HIP_OK(hipMemsetAsync(zerr.p, 0, 64, ws.stream)); }
     int64_t n_lines[2] = { 0, 0 };
     size_t max_scan = 0;
     for (int k = 0; k < n_texts; ++k) max_scan = std::max(max_scan, (size_t)fastq_n_chunks((int64_t)n_text[k]));
@@ -1880,12 +1896,26 @@ static bool upload_fastq(bwaidx_s* ix, const char* const text[2], const size_t n
     for (int k = 0; k < n_texts; ++k) {
         const int64_t n = (int64_t)n_text[k], nc = fastq_n_chunks(n);
         if (!(txt[k].ensure((size_t)n + 16) && counts[k].ensure((size_t)nc * 4) && base[k].ensure(((size_t)nc + 1) * 8))) return false;
-        if (n) HIP_OK(hipMemcpyAsync(txt[k].p, text[k], (size_t)n, hipMemcpyHostToDevice, ws.stream));
+        if (src.gz[k]) {
+            const size_t nm = src.mem[k].size();
+            if (!(zc[k].ensure(src.n_gz[k] + 32) && zm[k].ensure(nm * sizeof(BgzfMember) + 16))) return false;
+            HIP_OK(hipMemcpyAsync(zc[k].p, src.gz[k], src.n_gz[k], hipMemcpyHostToDevice, ws.stream));
+            if (nm) HIP_OK(hipMemcpyAsync(zm[k].p, src.mem[k].data(), nm * sizeof(BgzfMember), hipMemcpyHostToDevice, ws.stream));
+            TIMED(ws, K_OTHER, launch_bgzf_inflate(ws.stream, zc[k].as<uint8_t>(), zm[k].as<BgzfMember>(), (int)nm, k == 1 && src.gz[0] ? (int)src.mem[0].size() : 0,
+                                                   txt[k].as<uint8_t>(), zerr.as<int32_t>()));
+        } else if (n) HIP_OK(hipMemcpyAsync(txt[k].p, src.text[k], (size_t)n, hipMemcpyHostToDevice, ws.stream));
         TIMED(ws, K_OTHER, launch_fastq_count(ws.stream, txt[k].as<uint8_t>(), n, counts[k].as<int32_t>()));
         TIMED(ws, K_OTHER, launch_scan(ws.stream, counts[k].as<int32_t>(), base[k].as<int64_t>(), (int)nc, scan_tmp.as<int64_t>()));
         HIP_OK(hipMemcpyAsync(&n_lines[k], base[k].as<int64_t>() + nc, 8, hipMemcpyDeviceToHost, ws.stream));
     }
-    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 1: the line counts
+    int32_t ze = 0;
+    if (inflate) HIP_OK(hipMemcpyAsync(&ze, zerr.p, 4, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 1: the line counts (and the inflate's error word)
+    if (ze) {
+        *bad_member = BGZI_NO_ERROR - ze;
+        fprintf(stderr, "[bwamem_hip] upload_fastq: BGZF member %lld does not inflate (invalid deflate data, or a size or CRC-32 that does not match)\n", (long long)*bad_member);
+        timed_collect(ws); return true;
+    }
     for (int k = 0; k < n_texts; ++k)
         if (n_lines[k] < 0 || (n_lines[k] & 3)) { fprintf(stderr, "[bwamem_hip] upload_fastq: text %d has %lld lines, not a multiple of four\n", k + 1, (long long)n_lines[k]); timed_collect(ws); return true; }
     if (n_texts == 2 && n_lines[0] != n_lines[1]) { fprintf(stderr, "[bwamem_hip] upload_fastq: %lld records in the first text, %lld in the second\n", (long long)(n_lines[0] >> 2), (long long)(n_lines[1] >> 2)); timed_collect(ws); return true; }
@@ -1967,10 +1997,107 @@ bwamem_batch_t* bwamem_hip_batch_upload_fastq(bwaidx_t* idx, const char* text1, 
         if (n1 >= ((size_t)1 << 31) || n2 >= ((size_t)1 << 31) || n1 + n2 >= ((size_t)1 << 31)) { fprintf(stderr, "[bwamem_hip] upload_fastq: a call is one request under 2 GiB\n"); return 0; }
         std::lock_guard<std::mutex> lk(idx->mu);
         if (hipSetDevice(idx->device) != hipSuccess) return 0;
-        const char* const text[2] = { text1, text2 }; const size_t n_text[2] = { n1, n2 };
-        int64_t bad = -1; bwamem_batch_s* made = nullptr;
-        if (!upload_fastq(idx, text, n_text, text2 ? 2 : 1, &bad, &made)) return 0;
+        FastqSource src;
+        src.n_texts = text2 ? 2 : 1; src.text[0] = text1; src.text[1] = text2; src.n_text[0] = n1; src.n_text[1] = n2;
+        int64_t bad = -1, bad_member = -1; bwamem_batch_s* made = nullptr;
+        if (!upload_fastq(idx, src, &bad, &bad_member, &made)) return 0;
         if (!made && bad_record) *bad_record = bad;
+        return made;
+    });
+}
+
+// The member table of the stream p[0, n) (bgzf_inflate.h).  0: BGZF, mem and *text_bytes filled in; 1: the first member is not
+// BGZF's; 2: refused with a message, *bad_member = the offending member of this stream, or -1
+static int bgzf_member_table(const uint8_t* p, size_t n, std::vector<BgzfMember>& mem, int64_t* text_bytes, int64_t* bad_member)
+{
+    mem.clear(); *text_bytes = 0; *bad_member = -1;
+    for (size_t at = 0; at < n; ) {
+        BgzfMember m;
+        const int rc = bgzf_walk_member(p, n, at, &m);
+        if (rc == 1 && mem.empty()) return 1;
+        if (rc) {
+            *bad_member = (int64_t)mem.size();
+            fprintf(stderr, "[bwamem_hip] bgzf: member %zu at byte %zu: %s\n", mem.size(), at,
+                    rc == 1 ? "no BGZF header (bad magic, or no BC subfield)" : rc == 2 ? "its BSIZE does not fit the data (truncated?)" : "ISIZE over 65536");
+            return 2;
+        }
+        m.uoff = *text_bytes; *text_bytes += m.isize;
+        if (*text_bytes >= ((int64_t)1 << 31) || mem.size() >= 0x7ffffff0u) { fprintf(stderr, "[bwamem_hip] bgzf: a call is one request under 2 GiB\n"); return 2; }
+        mem.push_back(m);
+        at += (size_t)m.csize;
+    }
+    return 0;
+}
+
+void* bwamem_hip_bgzf_inflate_device(bwaidx_t* idx, const void* src, size_t n, size_t* pBytes, int64_t* bad_member)
+{
+    if (pBytes) *pBytes = 0;
+    if (bad_member) *bad_member = -1;
+    return guarded("bwamem_hip_bgzf_inflate_device", (void*)0, [&]() -> void* {
+        if (!idx || (n && !src)) return nullptr;
+        std::vector<BgzfMember> mem;
+        int64_t total = 0, bm = -1;
+        const int kind = bgzf_member_table((const uint8_t*)src, n, mem, &total, &bm);
+        if (kind == 1) { fprintf(stderr, "[bwamem_hip] bgzf_inflate_device: not a BGZF stream\n"); return nullptr; }
+        if (kind == 2) { if (bad_member) *bad_member = bm; return nullptr; }
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (hipSetDevice(idx->device) != hipSuccess) return nullptr;
+        Workspace& ws = idx->ws;
+        if (!ws.stream && hipStreamCreate(&ws.stream) != hipSuccess) return nullptr;
+        void* res = malloc(total ? (size_t)total : 1);
+        if (!res) return nullptr;
+        std::unique_ptr<void, void (*)(void*)> own(res, free);
+        if (mem.empty()) return own.release();
+        DevBuf zc, zm, txt, zerr;
+        const size_t nm = mem.size();
+        if (!(zc.ensure(n + 32) && zm.ensure(nm * sizeof(BgzfMember)) && txt.ensure((size_t)total + 16) && zerr.ensure(64))) return nullptr;
+        int32_t e = 0;
+        if (hipMemsetAsync(zerr.p, 0, 64, ws.stream) != hipSuccess || hipMemcpyAsync(zc.p, src, n, hipMemcpyHostToDevice, ws.stream) != hipSuccess
+            || hipMemcpyAsync(zm.p, mem.data(), nm * sizeof(BgzfMember), hipMemcpyHostToDevice, ws.stream) != hipSuccess) return nullptr;
+        launch_bgzf_inflate(ws.stream, zc.as<uint8_t>(), zm.as<BgzfMember>(), (int)nm, 0, txt.as<uint8_t>(), zerr.as<int32_t>());
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&e, zerr.p, 4, hipMemcpyDeviceToHost, ws.stream) != hipSuccess
+            || hipStreamSynchronize(ws.stream) != hipSuccess) return nullptr;
+        if (e) {
+            if (bad_member) *bad_member = BGZI_NO_ERROR - e;
+            fprintf(stderr, "[bwamem_hip] bgzf_inflate_device: member %d does not inflate (invalid deflate data, or a size or CRC-32 that does not match)\n", BGZI_NO_ERROR - e);
+            return nullptr;
+        }
+        if (total && hipMemcpy(res, txt.p, (size_t)total, hipMemcpyDeviceToHost) != hipSuccess) return nullptr;
+        if (pBytes) *pBytes = (size_t)total;
+        return own.release();
+    });
+}
+
+bwamem_batch_t* bwamem_hip_batch_upload_fastq_gz(bwaidx_t* idx, const void* gz1, size_t n1, const void* gz2, size_t n2, int64_t* bad_record, int64_t* bad_member)
+{
+    if (bad_record) *bad_record = -1;
+    if (bad_member) *bad_member = -1;
+    return guarded("bwamem_hip_batch_upload_fastq_gz", (bwamem_batch_t*)0, [&]() -> bwamem_batch_t* {
+        if (!idx || (!gz1 && n1) || (!gz2 && n2)) return 0;
+        FastqSource src;
+        src.n_texts = gz2 ? 2 : 1;
+        const uint8_t* const gz[2] = { (const uint8_t*)gz1, (const uint8_t*)gz2 }; const size_t n_gz[2] = { n1, n2 };
+        std::vector<char> host_text[2];
+        int64_t member0 = 0;
+        for (int k = 0; k < src.n_texts; ++k) {
+            int64_t tb = 0, bm = -1;
+            const int kind = n_gz[k] ? bgzf_member_table(gz[k], n_gz[k], src.mem[k], &tb, &bm) : 0;
+            if (kind == 2) { if (bad_member && bm >= 0) *bad_member = member0 + bm; return 0; }
+            if (kind == 0 && n_gz[k]) { src.gz[k] = gz[k]; src.n_gz[k] = n_gz[k]; src.n_text[k] = (size_t)tb; member0 += (int64_t)src.mem[k].size(); }
+            else if (kind == 1) {
+                if (!bwamem_gunzip_host(gz[k], n_gz[k], ((size_t)1 << 31) - 1, host_text[k])) return 0;
+                src.text[k] = host_text[k].data(); src.n_text[k] = host_text[k].size();
+            } else src.text[k] = "";
+            if (verbose()) fprintf(stderr, "[bwamem_hip] upload_fastq_gz: stream %d: %zu bytes, %s, %zu bytes of text\n", k + 1, n_gz[k],
+                                   src.gz[k] ? "BGZF, inflated on the device" : kind == 1 ? "plain gzip, inflated on the host (libz)" : "empty", src.n_text[k]);
+        }
+        if (src.n_text[0] + src.n_text[1] >= ((size_t)1 << 31)) { fprintf(stderr, "[bwamem_hip] upload_fastq_gz: a call is one request under 2 GiB\n"); return 0; }
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (hipSetDevice(idx->device) != hipSuccess) return 0;
+        int64_t bad = -1, bm = -1; bwamem_batch_s* made = nullptr;
+        if (!upload_fastq(idx, src, &bad, &bm, &made)) return 0;
+        if (!made && bad_record) *bad_record = bad;
+        if (!made && bad_member) *bad_member = bm;
         return made;
     });
 }

@@ -31,6 +31,7 @@
 #include <errno.h>
 #include <unistd.h>
 #include <dlfcn.h>
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -86,11 +87,24 @@ struct Zlib {                                           // compress2 and crc32 o
     typedef int (*compress2_t)(unsigned char*, unsigned long*, const unsigned char*, unsigned long, int);
     typedef unsigned long (*crc32_t)(unsigned long, const unsigned char*, unsigned int);
     compress2_t compress2 = nullptr; crc32_t crc32 = nullptr;
+    // ... and its inflate, for plain gzip streams (bwamem_gunzip_host).  z_stream as zlib 1.2 and later lay it out.
+    struct Stream {
+        const unsigned char* next_in; unsigned avail_in; unsigned long total_in;
+        unsigned char* next_out; unsigned avail_out; unsigned long total_out;
+        const char* msg; void* state; void* zalloc; void* zfree; void* opaque; int data_type; unsigned long adler, reserved;
+    };
+    typedef int (*inflate_init2_t)(Stream*, int, const char*, int);
+    typedef int (*inflate_t)(Stream*, int);
+    typedef int (*inflate_end_t)(Stream*);
+    inflate_init2_t inflateInit2_ = nullptr; inflate_t inflate = nullptr; inflate_end_t inflateReset = nullptr, inflateEnd = nullptr;
     Zlib() {
         void* h = dlopen("libz.so.1", RTLD_NOW | RTLD_LOCAL);
         if (!h) return;
         compress2 = (compress2_t)dlsym(h, "compress2"); crc32 = (crc32_t)dlsym(h, "crc32");
         if (!compress2 || !crc32) compress2 = nullptr, crc32 = nullptr;
+        inflateInit2_ = (inflate_init2_t)dlsym(h, "inflateInit2_"); inflate = (inflate_t)dlsym(h, "inflate");
+        inflateReset = (inflate_end_t)dlsym(h, "inflateReset"); inflateEnd = (inflate_end_t)dlsym(h, "inflateEnd");
+        if (!inflateInit2_ || !inflate || !inflateReset || !inflateEnd) inflateInit2_ = nullptr;
     }
 };
 const Zlib& zlib() { static const Zlib z; return z; }
@@ -181,6 +195,44 @@ struct BatchOwner { bwamem_batch_t* b; ~BatchOwner() { bwamem_hip_batch_free(b);
 
 // the contig names and lengths of an open index (pipeline.cpp)
 const std::vector<ContigInfo>& bwamem_index_contigs(const bwaidx_t* idx);
+
+// A plain gzip stream (one or several concatenated members, as `gzip` writes them) inflated on the host through libz.so.1: such a
+// stream has no member sizes and cannot be cut for the device (bgzf_inflate.h).  false with a message when the library is not
+// there, the stream is damaged, or the text would exceed `limit` bytes.  (pipeline.cpp: bwamem_hip_batch_upload_fastq_gz)
+bool bwamem_gunzip_host(const void* src, size_t n, size_t limit, std::vector<char>& out)
+{
+    const Zlib& z = zlib();
+    out.clear();
+    if (!z.inflateInit2_) { fprintf(stderr, "[bwamem_hip] gunzip: libz.so.1 could not be loaded, and a plain gzip stream is inflated on the host; recompress the file with bgzip (BGZF is inflated on the device)\n"); return false; }
+    Zlib::Stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (z.inflateInit2_(&zs, 15 + 16, "1", (int)sizeof zs) != 0) { fprintf(stderr, "[bwamem_hip] gunzip: inflateInit2 failed\n"); return false; }
+    bool ok = true;
+    size_t in_at = 0, have = 0;
+    out.resize(std::min(limit, std::max<size_t>(4 * n, 1 << 16)) + 1);
+    for (;;) {
+        if (zs.avail_in == 0 && in_at < n) { const size_t c = std::min<size_t>(n - in_at, 1u << 30); zs.next_in = (const unsigned char*)src + in_at; zs.avail_in = (unsigned)c; in_at += c; }
+        if (have == out.size()) {
+            if (have > limit) { fprintf(stderr, "[bwamem_hip] gunzip: a call is one request under 2 GiB\n"); ok = false; break; }
+            out.resize(std::min(limit + 1, out.size() * 2));
+        }
+        const size_t room = std::min<size_t>(out.size() - have, 1u << 30);
+        zs.next_out = (unsigned char*)out.data() + have; zs.avail_out = (unsigned)room;
+        const int rc = z.inflate(&zs, 0);
+        have += room - zs.avail_out;
+        if (rc == 1) {                                              // the end of a member: another may follow
+            if (zs.avail_in == 0 && in_at == n) break;
+            if (z.inflateReset(&zs) != 0) { ok = false; break; }
+        } else if (rc != 0 && !(rc == -5 && zs.avail_out == 0)) {    // (Z_BUF_ERROR with no room left only asks for more room)
+            fprintf(stderr, "[bwamem_hip] gunzip: not a valid gzip stream (%s)\n", zs.msg ? zs.msg : rc == -5 ? "truncated" : "error");
+            ok = false; break;
+        }
+    }
+    z.inflateEnd(&zs);
+    if (ok && have > limit) { fprintf(stderr, "[bwamem_hip] gunzip: a call is one request under 2 GiB\n"); ok = false; }
+    if (ok) out.resize(have); else out.clear();
+    return ok;
+}
 
 extern "C" {
 
@@ -581,7 +633,7 @@ int request_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, c
 }
 
 int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
-                      const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header)
+                      const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, bool gz = false)
 {
     try {
         if (!idx || !opt || fd < 0) return -1;
@@ -589,7 +641,8 @@ int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, con
         int32_t flag; memcpy(&flag, (const char*)opt + 60, 4);                  // mem_opt_t.flag (BwaMemAligner.java:75)
         const int paired = (flag & 0x2) != 0;
         int64_t bad = -1;
-        BatchOwner bo{ bwamem_hip_batch_upload_fastq(idx, text1, n1, text2, n2, &bad) };
+        int64_t bad_member = -1;
+        BatchOwner bo{ gz ? bwamem_hip_batch_upload_fastq_gz(idx, text1, n1, text2, n2, &bad, &bad_member) : bwamem_hip_batch_upload_fastq(idx, text1, n1, text2, n2, &bad) };
         if (!bo.b) return -1;
         if (rg_line && bwamem_hip_batch_set_read_group(bo.b, rg_line) != 0) return -1;
         if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
@@ -630,6 +683,16 @@ int bwamem_hip_align_fastq_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, co
 {
     if (counts) memset(counts, 0, sizeof *counts);
     return fastq_to_bam_file("align_fastq_to_marked_bam", idx, opt, pes, text1, n1, text2, n2, rg_line, 1, counts, sort, fd, fd_bai, write_header);
+}
+
+// ... from compressed FASTQ (bgzf_inflate.h): BGZF streams are inflated on the device, plain gzip streams on the host.  mark_dup == 0
+// (and counts == NULL) is bwamem_hip_align_fastq_to_bam on the inflated texts.
+int bwamem_hip_align_fastq_gz_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* gz1, size_t n1, const void* gz2, size_t n2,
+                                            const char* rg_line, int sort, int fd, int fd_bai, int write_header, int mark_dup, bwamem_dup_counts_t* counts)
+{
+    if (counts) memset(counts, 0, sizeof *counts);
+    return fastq_to_bam_file("align_fastq_gz_to_marked_bam", idx, opt, pes, (const char*)gz1, n1, (const char*)gz2, n2, rg_line, mark_dup != 0, mark_dup ? counts : nullptr,
+                             sort, fd, fd_bai, write_header, true);
 }
 
 }  // extern "C"

@@ -246,6 +246,32 @@ int    bwamem_hip_align_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const
 int    bwamem_hip_align_fastq_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2,
                                             size_t n2, const char* rg_line, int sort, int fd, int fd_bai, int write_header, bwamem_dup_counts_t* counts);
 
+/* Compressed FASTQ in (csrc/bgzf_inflate.h; additive): .fastq.gz bytes are taken as they are.  A BGZF stream -- what bgzip and this
+ * library's own compressor write: independent gzip members of at most 64 KiB of text -- is uploaded compressed and inflated in HBM,
+ * one wavefront per member; the host only walks the member headers, and the parse kernels of _upload_fastq run on the resident
+ * text.  A plain gzip stream (what gzip writes: no member sizes, nothing to cut) is inflated on the host through libz.so.1, loaded
+ * at run time, and its text takes the plain-text path; without that library such a stream is refused with a message that says to
+ * use bgzip.  The first member decides a stream's kind; the two streams of a call may differ in kind.  With BWAMEM_HIP_VERBOSE a
+ * line per stream says which way it went.
+ *   bwamem_hip_bgzf_inflate_device   host bytes in, inflated bytes out (jnibwa_free): the counterpart of
+ *                   bwamem_hip_bgzf_compress_device; idx selects the device.  BGZF only.  The empty stream gives zero bytes (not
+ *                   NULL).  NULL with *bad_member = the smallest offending member (-1 for errors of no single member: not BGZF,
+ *                   2 GiB of text or more) when the stream is refused: the rules are at the top of csrc/bgzf_inflate.h, and what
+ *                   they accept and refuse is what zlib accepts and refuses.
+ *   _upload_fastq_gz   exactly the batch _upload_fastq yields for the inflated texts -- payload, offsets, names, qualities, and
+ *                   *bad_record for malformed FASTQ inside good members; lines and records may straddle members anywhere.  gz2 ==
+ *                   NULL: one stream.  *bad_member counts the members of the first stream, then of the second (-1: none, or a
+ *                   damaged plain gzip stream).  "One request under 2 GiB" holds for the inflated texts and is checked before
+ *                   anything is uploaded.
+ *   bwamem_hip_align_fastq_gz_to_marked_bam   bwamem_hip_align_fastq_to_marked_bam with the texts replaced by such streams;
+ *                   mark_dup == 0 leaves the marking out (counts, when given, is zeroed): bwamem_hip_align_fastq_to_bam. */
+void*  bwamem_hip_bgzf_inflate_device(bwaidx_t* idx, const void* src, size_t n, size_t* pBytes, int64_t* bad_member);      /* jnibwa_free */
+bwamem_batch_t* bwamem_hip_batch_upload_fastq_gz(bwaidx_t* idx, const void* gz1, size_t n1, const void* gz2, size_t n2, int64_t* bad_record,
+                                                 int64_t* bad_member);
+int    bwamem_hip_align_fastq_gz_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* gz1, size_t n1, const void* gz2,
+                                               size_t n2, const char* rg_line, int sort, int fd, int fd_bai, int write_header, int mark_dup,
+                                               bwamem_dup_counts_t* counts);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
