@@ -79,6 +79,7 @@ struct DevIndex {
     int64_t  l_pac;
     int32_t  n_seqs, sa_intv, log_tab_n, sa_shift;   // sa_intv = 1 << sa_shift
     int32_t  n_cu, lds_bytes;                        // of the device the index lives on (launch geometry; host side only)
+    int32_t  lds_cu, pad_;                           // LDS of one CU (lds_bytes: the most one workgroup may ask for)
 };
 
 struct Intv { uint64_t x0, x1, size, info; };          // info = start<<32 | end

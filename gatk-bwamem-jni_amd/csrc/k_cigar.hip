@@ -586,6 +586,10 @@ void launch_gcigar(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const 
 {
     if (n_jobs <= 0) return;
     int z_lds_cap = 6144;                                            // covers bands of ~40 columns x 150 rows; larger matrices go to the HBM pool
+    // tiles of short reads run beside the seeding grid, which leaves 14 KB of a CU's LDS (launch_seed): with every matrix in
+    // the pool a workgroup asks for 3.3 KB (three 1 280-byte blocks) instead of 9.4 KB (eight), and three fit there instead of
+    // one.  The small matrices stay in L2, and the kernel is no slower alone
+    if (!slab_bytes && tv.max_len + 1 <= 3 * 64) z_lds_cap = 0;
     { const char* e = getenv("BWAMEM_HIP_ZLDS"); if (e && atoi(e) >= 0) z_lds_cap = atoi(e); }
     size_t cap = (size_t)tv.max_len + 2;
     // rows of the wave form: rings that hold the widest band mem_reg2aln asks for (opt.w << 2) -- or the whole read when that

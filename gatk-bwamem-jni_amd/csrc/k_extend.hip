@@ -1009,7 +1009,8 @@ void launch_extend(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const 
         return;
     }
     // every query of a tile whose reads are at most 3 * 64 - 1 bases long takes the register form: no rows in LDS, only the
-    // read -- which matters for overlap, because k_seed fills the CUs' LDS and a workgroup that asks for 2 KB finds no room
+    // read (one 1 280-byte block).  That matters for overlap: while a seeding chunk is resident a CU has 14 KB of LDS free
+    // (launch_seed), and the registers k_seed's nine waves leave are used up before eleven one-block workgroups are
     if (tv.max_len + 1 <= 3 * WAVE) { hipLaunchKernelGGL(k_extend_short, dim3(tv.n_reads), dim3(64), ((size_t)tv.max_len + 2 + 15) & ~(size_t)15, st, ix, opt, tv); return; }
     const size_t shmem = extend_lds_bytes(opt, tv.max_len);
     if (shmem >= 8192) hipLaunchKernelGGL(k_extend_long, dim3(tv.n_reads), dim3(64), shmem, st, ix, opt, tv);

@@ -162,6 +162,13 @@ __global__ void k_encode(uint8_t* seq, int64_t n_bytes)
 // stack index of the next candidate is a popcount; probing is on for min_seed_len <= 32.
 enum { S_IDLE = 0, S_NEXT = 1, S_FWD = 2, S_P3 = 3, S_BWD = 4, S_PRB0 = 5, S_PRB = 6 };      // (the states that walk to the left are the last three)
 #define SEED_EL_CAP 4
+// gfx950 sets LDS aside in blocks of 320 dwords (measured with tests/gpu_units/lds_granule.hip: one-wave workgroups asking for
+// 8 193 / 8 705 / 9 217 / 15 361 / 16 144 bytes are resident 18 / 18 / 16 / 9 / 9 to a CU of 163 840 bytes)
+#define SEED_LDS_GRANULE ((size_t)1280)
+// seeding workgroups' worth of LDS left free per CU beside short-read tiles.  None: nine workgroups of 150-base reads leave
+// 14 KB as it is, and an eighth instead of a ninth wave costs k_seed 6 % -- one workgroup's worth bought 1 % of the step on the
+// i.i.d. genome and lost 8-10 % on the human-like one (BWAMEM_HIP_SEED_RESERVE sets it in bytes)
+#define SEED_LDS_RESERVE_WG 0
 DEV uint32_t low_bits(int n) { return n <= 0 ? 0u : n >= 32 ? ~0u : (1u << n) - 1u; }
 
 template <bool LDSQ>
@@ -722,8 +729,33 @@ void launch_encode(hipStream_t st, uint8_t* seq, int64_t n_bytes)
     if (nb > 8192) nb = 8192;
     hipLaunchKernelGGL(k_encode, dim3((unsigned)nb), dim3(256), 0, st, seq, n_bytes);
 }
+SeedLdsPlan seed_lds_plan(size_t lds_per_cu, size_t granule, int max_len, bool narrow, int K, size_t reserve)
+{
+    SeedLdsPlan p;
+    if (granule < 1) granule = 1;
+    if (max_len < 0) max_len = 0;
+    const size_t qbytes = (size_t)64 * 4 * (((size_t)max_len + 7) / 8);
+    p.ldsq = qbytes <= 24576;                                        // the lanes' reads are staged in LDS up to here
+    p.lds = (size_t)(narrow ? 5 * K * 32 : 3 * K * 64) * 4 + (size_t)SEED_EL_CAP * 64 * 4 + (p.ldsq ? qbytes : 0) + 16;
+    const size_t alloc = (p.lds + granule - 1) / granule * granule;  // what the CU sets aside for one workgroup
+    p.reserve = alloc + reserve <= lds_per_cu ? reserve : lds_per_cu > alloc ? lds_per_cu - alloc : 0;
+    const size_t fit = lds_per_cu > p.reserve ? (lds_per_cu - p.reserve) / alloc : 0;
+    p.wpc = fit < 1 ? 1 : fit > 16 ? 16 : (int)fit;
+    return p;
+}
+extern "C" int bwamem_hip_seed_lds_plan(int64_t lds_per_cu, int64_t granule, int max_len, int narrow, int K, int64_t reserve, int64_t* lds_bytes, int* wpc)
+{
+    if (lds_per_cu <= 0 || granule <= 0 || max_len < 0 || K <= 0 || (K & (K - 1)) || reserve < 0) return -1;
+    const SeedLdsPlan p = seed_lds_plan((size_t)lds_per_cu, (size_t)granule, max_len, narrow != 0, K, (size_t)reserve);
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds;
+    if (wpc) *wpc = p.wpc;
+    return p.reserve == (size_t)reserve ? 0 : 1;
+}
 // k_seed is a persistent grid: as many one-wave workgroups as fit the CUs' LDS (the candidate stacks dominate), each
-// pulling reads from the tile's queue (tv.err[8], zeroed by the caller with the other flags).
+// pulling reads from the tile's queue (tv.err[8], zeroed by the caller with the other flags).  A workgroup leaves only when
+// the queue is dry, so what the grid takes is held for the whole chunk, and a workgroup too many would stay pending in the
+// high-priority queue until then: seed_lds_plan counts in the blocks the device allocates, and can keep a reserve free for
+// the tiles running beside the chunk (SEED_LDS_RESERVE_WG, BWAMEM_HIP_SEED_RESERVE).
 void launch_seed(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv)
 {
     if (tv.n_reads <= 0) return;
@@ -733,12 +765,19 @@ void launch_seed(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const Ti
     { const char* e = getenv("BWAMEM_HIP_SEED_K"); if (e && atoi(e) > 0) K = atoi(e); }
     { const char* e = getenv("BWAMEM_HIP_SEED_WPC"); if (e && atoi(e) > 0) wpc = atoi(e); }
     while (K & (K - 1)) K &= K - 1;                                  // the candidate ring needs a power of two
-    const size_t qbytes = (size_t)64 * 4 * (((size_t)tv.max_len + 7) / 8);
-    const bool ldsq = qbytes <= 24576;
     int narrow = ix.seq_len < (1ull << 35) && tv.max_len < 1023;
     { const char* e = getenv("BWAMEM_HIP_SEED_NARROW"); if (e) narrow = narrow && atoi(e) != 0; }
-    const size_t lds = (size_t)(narrow ? 5 * K * 32 : 3 * K * 64) * 4 + (size_t)SEED_EL_CAP * 64 * 4 + (ldsq ? qbytes : 0) + 16;
-    if (!wpc) { wpc = (int)((size_t)(160 * 1024) / ((lds + 1023) & ~(size_t)1023)); wpc = wpc < 1 ? 1 : wpc > 16 ? 16 : wpc; }
+    const size_t lds_cu = ix.lds_cu > 0 ? (size_t)ix.lds_cu : (size_t)160 << 10;
+    SeedLdsPlan plan = seed_lds_plan(lds_cu, SEED_LDS_GRANULE, tv.max_len, narrow != 0, K, 0);
+    {   // the reserve: by default only under tiles of the register forms (launch_extend: reads of up to 3 * 64 - 1 bases)
+        size_t reserve = tv.max_len + 1 <= 3 * 64 ? (size_t)SEED_LDS_RESERVE_WG * ((plan.lds + SEED_LDS_GRANULE - 1) / SEED_LDS_GRANULE * SEED_LDS_GRANULE) : 0;
+        const char* e = getenv("BWAMEM_HIP_SEED_RESERVE");           // bytes per CU, for reads of any length
+        if (e && atoll(e) >= 0) reserve = (size_t)atoll(e);
+        if (reserve) plan = seed_lds_plan(lds_cu, SEED_LDS_GRANULE, tv.max_len, narrow != 0, K, reserve);
+    }
+    const size_t lds = plan.lds;
+    const bool ldsq = plan.ldsq;
+    if (!wpc) wpc = plan.wpc;
     const int groups = (tv.n_reads + 63) / 64;
     int grid = groups < n_cu * wpc ? groups : n_cu * wpc;
     if (tv.smem_groups > 0 && grid > tv.smem_groups) grid = tv.smem_groups;

@@ -14,6 +14,12 @@ void launch_sa_densify(hipStream_t st, const DevIndex& ix, const uint64_t* sa_sr
 void launch_encode(hipStream_t st, uint8_t* seq, int64_t n_bytes);
 void launch_unpack_pac(hipStream_t st, const DevIndex& ix, int64_t start, int64_t n, uint8_t* dst);
 void launch_seed(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv);
+// LDS plan of the persistent seeding grid (pure host arithmetic): the dynamic LDS one k_seed workgroup asks for, whether it
+// stages its reads there, and how many workgroups go on a CU so that wpc * round_up(lds, granule) + reserve <= lds_per_cu.
+// wpc is at least 1 (a reserve that one workgroup does not leave is cut down to what it leaves: `reserve` says what holds)
+// and at most 16, the wave slots k_seed's registers allow.
+struct SeedLdsPlan { size_t lds, reserve; int wpc; bool ldsq; };
+SeedLdsPlan seed_lds_plan(size_t lds_per_cu, size_t granule, int max_len, bool narrow, int K, size_t reserve);
 size_t scan_tmp_bytes(int64_t n);
 void launch_scan(hipStream_t st, const int32_t* in, int64_t* out, int n, int64_t* tmp);   // tmp: scan_tmp_bytes(n), or null (one-workgroup form)
 void launch_order(hipStream_t st, const int32_t* n_seeds, int n, int32_t* bins64, int32_t* order);   // TileView::order

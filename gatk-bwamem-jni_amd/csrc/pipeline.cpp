@@ -434,6 +434,10 @@ static bool upload_index(bwaidx_s* ix)
         int v = 0;
         d.n_cu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ix->device) == hipSuccess && v > 0 ? v : 256;
         d.lds_bytes = hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ix->device) == hipSuccess && v > 0 ? v : 64 << 10;
+        d.lds_cu = d.lds_bytes;                                      // a CU has at least what one workgroup may ask for
+#ifdef __HIP_PLATFORM_AMD__                                          // (the tests' host emulation of the runtime knows the two attributes above only)
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, ix->device) == hipSuccess && v >= d.lds_bytes) d.lds_cu = v;
+#endif
     }
     {   // suffix array: the image samples every h.sa_intv-th rank; keep it as dense as HBM comfortably allows (5 bytes per
         // kept rank, at most a quarter of what is free now), so that a lookup is a short LF-walk or none at all

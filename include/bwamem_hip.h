@@ -281,6 +281,13 @@ typedef struct {
     uint64_t n_tiles, n_retries;
 } bwamem_stats_t;
 
+/* Tooling (tests): the LDS plan of the persistent seeding grid, pure host arithmetic (csrc/kernels.h: seed_lds_plan).  For a CU
+ * with lds_per_cu bytes of LDS handed out in blocks of `granule` bytes, reads of up to max_len bases, the narrow (narrow != 0) or
+ * wide candidate rings of K entries (a power of two) and `reserve` bytes per CU to be left free: *lds_bytes = what one workgroup
+ * asks for, *wpc = workgroups per CU, 1..16, with wpc * round_up(lds_bytes, granule) + reserve <= lds_per_cu.  0 = ok; 1 = the
+ * reserve was cut to what one workgroup leaves; -1 = bad arguments. */
+int bwamem_hip_seed_lds_plan(int64_t lds_per_cu, int64_t granule, int max_len, int narrow, int K, int64_t reserve, int64_t* lds_bytes, int* wpc);
+
 void bwamem_hip_stats_enable(int on);          /* per-kernel HIP-event timing (off by default) */
 void bwamem_hip_stats_reset(void);
 void bwamem_hip_stats_get(bwamem_stats_t* out);
