@@ -111,8 +111,8 @@ static __device__ __forceinline__ int global_wave_diag_pk(const DevIndex& ix, co
             for (int p = 0; p < NP; ++p) { mx = pk_max(mx, (hd[p] & am[p]) | (FLIP & ~am[p])); nmn = pk_max(nmn, (~hd[p] & am[p]) | (FLIP & ~am[p])); }
             int rmax = pk_shalf(mx, 0) > pk_shalf(mx, 1) ? pk_shalf(mx, 0) : pk_shalf(mx, 1);
             int rnmn = pk_shalf(nmn, 0) > pk_shalf(nmn, 1) ? pk_shalf(nmn, 0) : pk_shalf(nmn, 1);
-            rmax = wave_max(rmax);
-            const int rmin = -wave_max(rnmn) - 1;
+            rmax = wave_max_u(rmax);
+            const int rmin = -wave_max_u(rnmn) - 1;
             if (rmax - rmin > fit.range) { ok = false; return 0; }
             const uint32_t D2 = pk_both(-rmax);
             base += rmax;
@@ -192,8 +192,8 @@ static __device__ __forceinline__ int global_wave_diag_pk(const DevIndex& ix, co
     int score = 0;
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-        if ((l_end >> 6) == p) score = pk_shalf((uint32_t)wave_bcast((int)hrow[p], l_end & 63), 0);
-        if ((l_end >> 6) == p + NP) score = pk_shalf((uint32_t)wave_bcast((int)hrow[p], l_end & 63), 1);
+        if ((l_end >> 6) == p) score = pk_shalf((uint32_t)wave_bcast_u((int)hrow[p], l_end & 63), 0);
+        if ((l_end >> 6) == p + NP) score = pk_shalf((uint32_t)wave_bcast_u((int)hrow[p], l_end & 63), 1);
     }
     score += base;
     return score;

@@ -50,12 +50,12 @@ static __device__ __forceinline__ int traceback(const uint8_t* z, bool z_lds, in
             const int run_ = nz_ ? __ffsll((long long)nz_) - 1 : 64; \
             if (run_ > 0) { TB_PUSH(0, run_); i -= run_; k -= run_; } \
             if (run_ < 64) { \
-                const int dn_ = __shfl(d_, run_); \
+                const int dn_ = wave_bcast_u(d_, run_); \
                 if (dn_ == 1) { TB_PUSH(2, 1); --i; which = 1; } \
                 else if (dn_ == 2) { TB_PUSH(1, 1); --k; which = 2; } \
             } \
         } else { \
-            which = GET(i, k) >> (which << 1) & 3; \
+            which = wave_uni(GET(i, k) >> (which << 1) & 3);      /* one cell, read by every lane: the walk state stays scalar */ \
             if (which == 0) { TB_PUSH(0, 1); --i; --k; } \
             else if (which == 1) { TB_PUSH(2, 1); --i; } \
             else { TB_PUSH(1, 1); --k; } \
@@ -134,7 +134,7 @@ static __device__ __forceinline__ int global_wave(const DevIndex& ix, const MemO
     __syncthreads();
     for (int i = 0; i < tlen; ++i) {
         if ((i & 63) == 0) { int ii = i + lane; tch = ii < tlen ? acc_t(ix, A, ii) : 4; }
-        const int tb = wave_bcast(tch, i & 63);
+        const int tb = wave_readlane(tch, i & 63);
         const int ms0 = score_at(ST.p[0], ST.n[0], tb), ms1 = score_at(ST.p[1], ST.n[1], tb), ms2 = score_at(ST.p[2], ST.n[2], tb), ms3 = score_at(ST.p[3], ST.n[3], tb), ms4 = score_at(ST.p[4], ST.n[4], tb);
         const int beg = i > w ? i - w : 0;
         const int end = i + w + 1 < qlen ? i + w + 1 : qlen;
@@ -171,8 +171,8 @@ static __device__ __forceinline__ int global_wave(const DevIndex& ix, const MemO
             e2 = e2 > t ? e2 : t;
             d |= (f - e_ins) > tins ? 2 << 4 : 0;
             int last = (end - 1 - c) < 63 ? (end - 1 - c) : 63;
-            hlast = wave_bcast(h, last);
-            int Plast = wave_bcast(P, 63);
+            hlast = wave_bcast_u(h, last);
+            int Plast = wave_bcast_u(P, 63);
             { int f1 = fcarry - WAVE * e_ins, f2 = Plast - (c + 63) * e_ins; fcarry = f1 > f2 ? f1 : f2; }
             if (act) { z_put(zi + (j - beg), (uint8_t)d, z_lds); L.eh_e[j & RM] = e2; L.eh_h[(j + 1) & RM] = h; }
         }
@@ -184,7 +184,7 @@ static __device__ __forceinline__ int global_wave(const DevIndex& ix, const MemO
         (void)hlast;
         __syncthreads();
     }
-    const int score = L.eh_h[qlen & RM];
+    const int score = wave_uni(L.eh_h[qlen & RM]);
     __syncthreads();
     return score;
 }
@@ -240,7 +240,7 @@ static __device__ __forceinline__ int global_wave_diag(const DevIndex& ix, const
         e = dpp_shl1(act ? e2 : MINUS_INF, MINUS_INF);
         qv = dpp_shl1(qv, qin);
     }
-    const int score = wave_bcast(h, qlen - 1 - (tlen - 1 - w));     // H(tlen-1, qlen-1); the caller checked that lane is in the band
+    const int score = wave_bcast_u(h, qlen - 1 - (tlen - 1 - w));     // H(tlen-1, qlen-1); the caller checked that lane is in the band
     return score;
 }
 
@@ -317,7 +317,7 @@ static __device__ __forceinline__ int global_wave_diag_n(const DevIndex& ix, con
     const int l_end = qlen - 1 - (tlen - 1 - w);                     // H(tlen-1, qlen-1); the caller checked that slot is in the band
     int score = MINUS_INF;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) if ((l_end >> 6) == c) score = wave_bcast(hrow[c], l_end & 63);
+    for (int c = 0; c < NCH; ++c) if ((l_end >> 6) == c) score = wave_bcast_u(hrow[c], l_end & 63);
     return score;
 }
 
@@ -481,14 +481,17 @@ __global__ void __launch_bounds__(64, MAXCH >= 13 ? 2 : 4) k_gcigar(DevIndex ix,
     // slabs != null (tiles of long reads): a resident grid pulls jobs from a queue and every workgroup keeps the traceback
     // matrix of its current job in a slab of its own -- megabytes per job, but bounded by the grid, not by the job count
   for (int job = blockIdx.x, first = 1; ; first = 0) {
-    if (slabs) { int nx = 0; if (lane == 0) nx = atomicAdd(queue, 1); job = __shfl(nx, 0); }
+    if (slabs) { int nx = 0; if (lane == 0) nx = atomicAdd(queue, 1); job = wave_bcast_u(nx, 0); }
     else if (!first) job += HBM ? (int)gridDim.x : n_jobs;
     if (job >= n_jobs) break;
     __syncthreads();                                                   // the previous job of this workgroup is done with the rows
-    if (outs[job].n_cigar >= 0) continue;                              // done by k_gcigar_lane
-    const DpJob jb = jobs[job];
-    const AlnReg ar = tv.regs[tv.seed_off[jb.read] + jb.reg];
-    const uint8_t* query = tv.seq + tv.seq_off[jb.read];
+    // one wavefront, one job: what steers the retry loop and the row loops is wave-uniform and kept scalar (wave_ops.h: wave_uni)
+    if (wave_uni(outs[job].n_cigar) >= 0) continue;                    // done by k_gcigar_lane
+    DpJob jb = jobs[job];
+    jb.read = wave_uni(jb.read); jb.reg = wave_uni(jb.reg);
+    AlnReg ar = tv.regs[wave_uni64(tv.seed_off[jb.read]) + jb.reg];
+    ar.rb = wave_uni64(ar.rb); ar.re = wave_uni64(ar.re); ar.qb = wave_uni(ar.qb); ar.qe = wave_uni(ar.qe); ar.truesc = wave_uni(ar.truesc);
+    const uint8_t* query = tv.seq + wave_uni64(tv.seq_off[jb.read]);
     const int cap = tv.max_len + 2;
     GLds L;
     uint8_t* sq;                                                       // the region's query bases, in alignment order
@@ -507,7 +510,7 @@ __global__ void __launch_bounds__(64, MAXCH >= 13 ? 2 : 4) k_gcigar(DevIndex ix,
     SeqAcc A; A.q = query + ar.qb; A.qlen = ar.qe - ar.qb; A.rev = ar.rb >= ix.l_pac; A.t0 = ar.rb; A.tlen = (int)(ar.re - ar.rb);
     uint32_t* cigar = cig_pool + (size_t)job * cig_cap;
     // the retry loop of mem_reg2aln around bwa_gen_cigar2 (all lanes take the same decisions)
-    int w2 = first_w2(opt, ar), i = 0, last_sc = -(1 << 30), score = 0, n_cigar = 0;
+    int w2 = wave_uni(first_w2(opt, ar)), i = 0, last_sc = -(1 << 30), score = 0, n_cigar = 0;
     const int l_query = A.qlen, rlen = A.tlen;
     const bool usable = !(l_query <= 0 || ar.rb >= ar.re || (ar.rb < ix.l_pac && ar.re > ix.l_pac) || ar.re > ix.l_pac << 1 || ar.rb < 0);
     bool deferred = false;                                             // band too wide for the LDS rings: the HBM kernel takes the job
@@ -526,6 +529,7 @@ __global__ void __launch_bounds__(64, MAXCH >= 13 ? 2 : 4) k_gcigar(DevIndex ix,
             w = w < w2 ? w : w2;
             min_w = d + 3;
             w = w > min_w ? w : min_w;
+            w = wave_uni(w);                                           // (div_plus divides in float: its quotient sits in a vector register)
             const int n_col = l_query < 2 * w + 1 ? l_query : 2 * w + 1;
             const unsigned long long need = (unsigned long long)n_col * (unsigned long long)rlen;
             uint8_t* z = z_lds;
@@ -533,7 +537,7 @@ __global__ void __launch_bounds__(64, MAXCH >= 13 ? 2 : 4) k_gcigar(DevIndex ix,
             else if (need > (unsigned long long)z_lds_cap) {             // traceback matrix too big for LDS: bump-allocate HBM
                 unsigned long long at = 0;
                 if (lane == 0) at = atomicAdd(zpool_cur, (need + 63ull) & ~63ull);
-                at = __shfl(at, 0);
+                at = wave_bcast_u64(at, 0);
                 if (at + need > zpool_cap) { err |= ERR_ZPOOL; break; }
                 z = zpool + at;
             }
@@ -557,7 +561,8 @@ __global__ void __launch_bounds__(64, MAXCH >= 13 ? 2 : 4) k_gcigar(DevIndex ix,
             else if (MAXCH >= 7 && diag_ok && nch <= 7) score = global_wave_diag_n<7>(ix, opt, sq, lane, A, w, z, z == z_lds, n_col);
             else if (MAXCH >= 13 && diag_ok && nch <= 13) score = global_wave_diag_n<13>(ix, opt, sq, lane, A, w, z, z == z_lds, n_col);
             else score = global_wave(ix, opt, L, lane, A, w, z, z == z_lds, n_col);
-            n_cigar = traceback(z, z == z_lds, n_col, w, rlen, l_query, lane, cigar, cig_cap, err, tile, K);
+            score = wave_uni(score);
+            n_cigar = wave_uni(traceback(z, z == z_lds, n_col, w, rlen, l_query, lane, cigar, cig_cap, err, tile, K));
             __syncthreads();
             if (score == last_sc || w2 == opt.w << 2) break;
             last_sc = score;

@@ -21,6 +21,12 @@ struct ExtRes { int score, qle, tle, gtle, gscore, max_off; };
 // of LDS for its rows, not 120 KB, and a CU holds ten such wavefronts instead of one.  (Rows in global memory: rm = ~0.)
 struct ExtLds { int32_t* eh_h; int32_t* eh_e; int32_t* tmpM; const uint8_t* query; int rm; };
 
+// The scalar arguments of an extension are the same in all 64 lanes (one wavefront works on one read).  Every form states that
+// at its entry (wave_ops.h: wave_uni), so that the row loop's bookkeeping -- window, maxima, z-drop and early-exit tests -- is
+// scalar arithmetic and scalar branches whatever the caller derived the arguments from.
+#define EXT_UNIFORM_ARGS() do { qlen = wave_uni(qlen); q0 = wave_uni(q0); qstep = wave_uni(qstep); tlen = wave_uni(tlen); t0 = wave_uni64(t0); \
+        tstep = wave_uni(tstep); w = wave_uni(w); end_bonus = wave_uni(end_bonus); zdrop = wave_uni(zdrop); h0 = wave_uni(h0); } while (0)
+
 // Early exit of the extension DP (both forms below).  Upstream's ksw_extend2 keeps computing rows until the target
 // runs out, the row maximum is 0 or the z-drop test fires; for a query that has been matched to its end that means
 // up to |query| further rows of slowly decaying deletion scores that change nothing.  After a row, every score a later
@@ -42,6 +48,7 @@ static __device__ ExtRes extend_wave(const DevIndex& ix, const MemOpt& opt, cons
                                      int qlen, int q0, int qstep, int tlen, int64_t t0, int tstep,
                                      int w, int end_bonus, int zdrop, int h0, unsigned long long& n_cells)
 {
+    EXT_UNIFORM_ARGS();
     const int o_del = opt.o_del, e_del = opt.e_del, o_ins = opt.o_ins, e_ins = opt.e_ins;
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
     int i, beg, end, max, max_i, max_j, max_ins, max_del, max_ie, gscore, max_off;
@@ -56,6 +63,7 @@ static __device__ ExtRes extend_wave(const DevIndex& ix, const MemOpt& opt, cons
         max_del = div_plus(qlen * mx + end_bonus - o_del, e_del, 1);
         max_del = max_del > 1 ? max_del : 1;
         w = w < max_del ? w : max_del;
+        w = wave_uni(w);                                   // (div_plus divides in float: its quotient sits in a vector register)
     }
     // first row: decay from h0 by insertion costs.  Index j of the row is H(-1, j-1); the ring holds indices 0 .. w + 1 now and
     // every row below adds the index the band is about to reach (no earlier row can have written it)
@@ -71,11 +79,12 @@ static __device__ ExtRes extend_wave(const DevIndex& ix, const MemOpt& opt, cons
             tch = ii < tlen ? ref_base2(ix, t0 + (int64_t)tstep * ii) : 4;
         }
         if (lane == 0 && i + w + 1 <= qlen) { L.eh_h[(i + w + 1) & RM] = EXT_INIT_H(i + w + 1); L.eh_e[(i + w + 1) & RM] = 0; }
-        const int tb = wave_bcast(tch, i & 63);
+        const int tb = wave_readlane(tch, i & 63);
         const int ms0 = score_at(ST.p[0], ST.n[0], tb), ms1 = score_at(ST.p[1], ST.n[1], tb), ms2 = score_at(ST.p[2], ST.n[2], tb), ms3 = score_at(ST.p[3], ST.n[3], tb), ms4 = score_at(ST.p[4], ST.n[4], tb);
         int m = 0, mj = -1, h1, h1i, hlast = 0;
         if (beg < i - w) beg = i - w;
         if (end > i + w + 1) end = i + w + 1;
+        end = wave_uni(end);                               // (or the two minima become one three-operand vector instruction)
         if (end > qlen) end = qlen;
         if (beg == 0) { h1i = h0 - (o_del + e_del * (i + 1)); if (h1i < 0) h1i = 0; }
         else h1i = 0;
@@ -141,14 +150,11 @@ static __device__ ExtRes extend_wave(const DevIndex& ix, const MemOpt& opt, cons
         if (m == 0) break;
         if (m > max) {
             max = m; max_i = i; max_j = mj;
-            int d = mj - i; d = d < 0 ? -d : d;
+            int d = mj - i; d = wave_uni(d < 0 ? -d : d);   // (as above: no three-operand vector maximum)
             max_off = max_off > d ? max_off : d;
-        } else if (zdrop > 0) {
-            if (i - max_i > mj - max_j) {
-                if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break;
-            } else {
-                if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break;
-            }
+        } else if (zdrop > 0) {                            // (one test for both sides of the diagonal: fewer scalar branches)
+            const int dd = (i - max_i) - (mj - max_j);
+            if (max - m - ((dd > 0 ? dd : 0) * e_del + (dd < 0 ? -dd : 0) * e_ins) > zdrop) break;
         }
         __syncthreads();
         // shrink the window to the non-zero span of the row just written
@@ -179,7 +185,7 @@ static __device__ ExtRes extend_wave(const DevIndex& ix, const MemOpt& opt, cons
             for (int c = beg; c < lim; c += WAVE) {
                 const int j = c + lane;
                 const int term = j < lim ? ext_bound_term(L.eh_h[j & RM], L.eh_e[j & RM], mx, qlen - 1 - j) : 0;
-                const int bc = wave_max(term);
+                const int bc = wave_max_u(term);
                 B = B > bc ? B : bc;
             }
             // indices beyond hold the untouched first row, whose terms fall with j: the first of them is the largest
@@ -203,6 +209,7 @@ static __device__ ExtRes extend_wave_reg(const DevIndex& ix, const MemOpt& opt, 
                                          int qlen, int q0, int qstep, int tlen, int64_t t0, int tstep,
                                          int w, int end_bonus, int zdrop, int h0, unsigned long long& n_cells)
 {
+    EXT_UNIFORM_ARGS();
     const int o_del = opt.o_del, e_del = opt.e_del, o_ins = opt.o_ins, e_ins = opt.e_ins;
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
     int i, beg, end, max, max_i, max_j, max_ins, max_del, max_ie, gscore, max_off;
@@ -231,6 +238,7 @@ static __device__ ExtRes extend_wave_reg(const DevIndex& ix, const MemOpt& opt, 
         max_del = div_plus(qlen * mx + end_bonus - o_del, e_del, 1);
         max_del = max_del > 1 ? max_del : 1;
         w = w < max_del ? w : max_del;
+        w = wave_uni(w);                                   // (div_plus divides in float: its quotient sits in a vector register)
     }
     max = h0; max_i = max_j = -1; max_ie = -1; gscore = -1; max_off = 0;
     beg = 0; end = qlen;
@@ -241,6 +249,7 @@ static __device__ ExtRes extend_wave_reg(const DevIndex& ix, const MemOpt& opt, 
         int m, mj, h1, h1i;
         if (beg < i - w) beg = i - w;
         if (end > i + w + 1) end = i + w + 1;
+        end = wave_uni(end);                               // (or the two minima become one three-operand vector instruction)
         if (end > qlen) end = qlen;
         if (beg == 0) { h1i = h0 - (o_del + e_del * (i + 1)); if (h1i < 0) h1i = 0; }
         else h1i = 0;
@@ -296,14 +305,11 @@ static __device__ ExtRes extend_wave_reg(const DevIndex& ix, const MemOpt& opt, 
         if (m == 0) break;
         if (m > max) {
             max = m; max_i = i; max_j = mj;
-            int d = mj - i; d = d < 0 ? -d : d;
+            int d = mj - i; d = wave_uni(d < 0 ? -d : d);   // (as above: no three-operand vector maximum)
             max_off = max_off > d ? max_off : d;
-        } else if (zdrop > 0) {
-            if (i - max_i > mj - max_j) {
-                if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break;
-            } else {
-                if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break;
-            }
+        } else if (zdrop > 0) {                            // (one test for both sides of the diagonal: fewer scalar branches)
+            const int dd = (i - max_i) - (mj - max_j);
+            if (max - m - ((dd > 0 ? dd : 0) * e_del + (dd < 0 ? -dd : 0) * e_ins) > zdrop) break;
         }
         {   // shrink the window to the non-zero span of the row just written
             int nb = end, jl = -2;
@@ -359,6 +365,7 @@ static __device__ ExtRes extend_wave_pk2(const DevIndex& ix, const MemOpt& opt, 
                                          int qlen, int q0, int qstep, int tlen, int64_t t0, int tstep,
                                          int w, int end_bonus, int zdrop, int h0, unsigned long long& n_cells)
 {
+    EXT_UNIFORM_ARGS();
     const int o_del = opt.o_del, e_del = opt.e_del, o_ins = opt.o_ins, e_ins = opt.e_ins;
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
     int i, beg, end, max, max_i, max_j, max_ins, max_del, max_ie, gscore, max_off;
@@ -392,28 +399,34 @@ static __device__ ExtRes extend_wave_pk2(const DevIndex& ix, const MemOpt& opt, 
         max_del = div_plus(qlen * mx + end_bonus - o_del, e_del, 1);
         max_del = max_del > 1 ? max_del : 1;
         w = w < max_del ? w : max_del;
+        w = wave_uni(w);                                   // (div_plus divides in float: its quotient sits in a vector register)
     }
     max = h0; max_i = max_j = -1; max_ie = -1; gscore = -1; max_off = 0;
     beg = 0; end = qlen;
     int tch = 4;
     for (i = 0; i < tlen; ++i) {
-        if ((i & 63) == 0) { int ii = i + lane; tch = ii < tlen ? ref_base2(ix, t0 + (int64_t)tstep * ii) : 4; }
-        const int tb = wave_readlane(tch, i & 63);
+        // 64 target bases at a time, one per lane, kept as the byte-permute selector that fetches both columns' scores against that
+        // base (pk16.h: pk_bytes2), so that a row's selector is one lane read and no scalar arithmetic
+        if ((i & 63) == 0) { int ii = i + lane; const uint32_t tc = ii < tlen ? (uint32_t)ref_base2(ix, t0 + (int64_t)tstep * ii) : 4u; tch = (int)(0x0c000c00u | (4u + tc) << 16 | tc); }
+        const uint32_t tsel = (uint32_t)wave_readlane(tch, i & 63);
         int m, mj, h1, h1i;
         if (beg < i - w) beg = i - w;
         if (end > i + w + 1) end = i + w + 1;
+        end = wave_uni(end);                               // (or the two minima become one three-operand vector instruction)
         if (end > qlen) end = qlen;
         if (beg == 0) { h1i = h0 - (o_del + e_del * (i + 1)); if (h1i < 0) h1i = 0; }
         else h1i = 0;
         h1 = h1i;
         const int pos1 = end > beg ? beg : end;            // the column whose eh.h becomes the first-column value
         const bool a_lo = lane >= beg && lane < end, a_hi = jhi >= beg && jhi < end;
+        // (ballots of the compares themselves, combined as scalars: the compares' own lane masks, no further instruction)
+        const unsigned long long b_lo = wave_ballot_b(lane >= beg) & wave_ballot_b(lane < end), b_hi = wave_ballot_b(jhi >= beg) & wave_ballot_b(jhi < end);
         const uint32_t am = (a_lo ? 0xffffu : 0u) | (a_hi ? 0xffff0000u : 0u);
         // M = live && Mp ? Mp + score : 0.  The scores sit in the lane as bytes biased by 128 (one byte permute fetches both columns'
         // scores against this row's base); "Mp == 0" is the sign of Mp - 1 (Mp >= 0).  Mb = M + 128 where the cell is alive, 0 where not:
         // the bias goes into the constants below, and a dead cell's -128 loses every maximum it enters just as its 0 would (E >= 0).
         const uint32_t Mp = ehh, e = ehe;
-        const uint32_t Mb = pk_add(Mp, pk_bytes(scp_lo, scp_hi, tb)) & am & ~pk_sra15(pk_sub(Mp, ONE));
+        const uint32_t Mb = pk_add(Mp, pk_perm(scp_hi, scp_lo, tsel)) & am & ~pk_sra15(pk_sub(Mp, ONE));
         const uint32_t M = pk_sub(Mb, BIAS);
         const uint32_t tt = pk_max(pk_sub(Mb, OEIB), 0u);
         uint32_t P = pk_add(tt, je);                                           // U, then its inclusive prefix maximum per half
@@ -433,7 +446,6 @@ static __device__ ExtRes extend_wave_pk2(const DevIndex& ix, const MemOpt& opt, 
         const int best = wave_readlane(dpp_prefix_max(klo > khi ? klo : khi, -1), 63);
         const uint32_t t2 = pk_max(pk_sub(Mb, OEDB), 0u);
         const uint32_t en = pk_max(pk_sub(e, ED), t2);
-        if (end > beg) { const int v = wave_readlane((int)h, (end - 1) & 63); h1 = ((end - 1) >> 6) ? v >> 16 : (int)(int16_t)(v & 0xffff); }
         // in-place row update: eh[pos1].h = h1i, eh[j+1].h = H(i,j) for the live columns, eh[j].e = E(i+1,j), eh[end].e = 0
         const uint32_t fill = (uint32_t)wave_readlane((int)h, 63) << 16 | 0xffffu;       // lane 0: nothing left of column 0, column 63 left of column 64
         const uint32_t hsh = (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)h, DPP_WAVE_SHR1, 0xf, 0xf, false);
@@ -444,16 +456,19 @@ static __device__ ExtRes extend_wave_pk2(const DevIndex& ix, const MemOpt& opt, 
             ehh = lane == (pos1 & 63) ? (ehh & ~half) | (pk_both(h1i) & half) : ehh;
         }
         ehe = (en & am) | (ehe & ~am);
+        const bool at_end = lane == (end & 63);
+        const unsigned long long b_end = wave_ballot_b(at_end);
         {
             const uint32_t half = (end >> 6) ? 0xffff0000u : 0xffffu;
-            ehe = lane == (end & 63) ? ehe & ~half : ehe;
+            ehe = at_end ? ehe & ~half : ehe;
         }
         m = best < 0 ? 0 : best >> 8;
         mj = best < 0 ? -1 : best & 255;
         if (end > beg) n_cells += (unsigned long long)(end - beg);
         {
             const int jafter = end > beg ? end : beg;
-            if (jafter == qlen) {
+            if (jafter == qlen) {                          // (H of the row's last column is only needed here)
+                if (end > beg) { const int v = wave_readlane((int)h, (end - 1) & 63); h1 = ((end - 1) >> 6) ? v >> 16 : (int)(int16_t)(v & 0xffff); }
                 max_ie = gscore > h1 ? max_ie : i;
                 gscore = gscore > h1 ? gscore : h1;
             }
@@ -461,21 +476,21 @@ static __device__ ExtRes extend_wave_pk2(const DevIndex& ix, const MemOpt& opt, 
         if (m == 0) break;
         if (m > max) {
             max = m; max_i = i; max_j = mj;
-            int d = mj - i; d = d < 0 ? -d : d;
+            int d = mj - i; d = wave_uni(d < 0 ? -d : d);   // (as above: no three-operand vector maximum)
             max_off = max_off > d ? max_off : d;
-        } else if (zdrop > 0) {
-            if (i - max_i > mj - max_j) {
-                if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break;
-            } else {
-                if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break;
-            }
+        } else if (zdrop > 0) {                            // (one test for both sides of the diagonal: fewer scalar branches)
+            const int dd = (i - max_i) - (mj - max_j);
+            if (max - m - ((dd > 0 ? dd : 0) * e_del + (dd < 0 ? -dd : 0) * e_ins) > zdrop) break;
         }
         {   // shrink the window to the non-zero span of the row just written
             const uint32_t nz = ehh | ehe;
-            const unsigned long long nzl = wave_ballot((nz & 0xffffu) != 0), nzh = wave_ballot((nz >> 16) != 0);
-            const unsigned long long fl = nzl & wave_ballot(a_lo), fh = nzh & wave_ballot(a_hi);
+            const unsigned long long nzl = wave_ballot_b((nz & 0xffffu) != 0), nzh = wave_ballot_b((nz >> 16) != 0);
+            const unsigned long long fl = nzl & b_lo, fh = nzh & b_hi;
             beg = fl ? __ffsll((long long)fl) - 1 : fh ? WAVE + __ffsll((long long)fh) - 1 : end;
-            const unsigned long long gl = nzl & wave_ballot(lane >= beg && lane <= end), gh = nzh & wave_ballot(jhi >= beg && jhi <= end);
+            // columns beg .. end of the new window: no live column below the new beg is non-zero (it is the first), so these are
+            // the non-zero live columns and column end itself -- scalar mask arithmetic instead of two more compares per half
+            const unsigned long long e_lo = end < WAVE ? b_end : 0ull, e_hi = end < WAVE ? 0ull : b_end;     // (end <= qlen < 128)
+            const unsigned long long gl = fl | (nzl & e_lo), gh = fh | (nzh & e_hi);
             const int jl = gh ? WAVE + 63 - __clzll((long long)gh) : gl ? 63 - __clzll((long long)gl) : beg - 1;
             end = jl + 2 < qlen ? jl + 2 : qlen;
         }
@@ -518,6 +533,7 @@ static __device__ ExtRes extend_wave_pkl(const DevIndex& ix, const MemOpt& opt, 
                                          int qlen, int q0, int qstep, int tlen, int64_t t0, int tstep,
                                          int w, int end_bonus, int zdrop, int h0, unsigned long long& n_cells)
 {
+    EXT_UNIFORM_ARGS();
     const int o_del = opt.o_del, e_del = opt.e_del, o_ins = opt.o_ins, e_ins = opt.e_ins;
     const int oe_del = o_del + e_del, oe_ins = o_ins + e_ins;
     int i, beg, end, max, max_i, max_j, max_ins, max_del, max_ie, gscore, max_off;
@@ -534,6 +550,7 @@ static __device__ ExtRes extend_wave_pkl(const DevIndex& ix, const MemOpt& opt, 
         max_del = div_plus(qlen * mx + end_bonus - o_del, e_del, 1);
         max_del = max_del > 1 ? max_del : 1;
         w = w < max_del ? w : max_del;
+        w = wave_uni(w);                                   // (div_plus divides in float: its quotient sits in a vector register)
     }
 #define PKL_INIT_H(j) ((j) == 0 ? h0 : h0 > oe_ins && h0 - oe_ins - ((j) - 1) * e_ins > 0 ? h0 - oe_ins - ((j) - 1) * e_ins : 0)
 #define PKL_SLOT(j) (((((j) >> 7) & NPM) << 6) + ((j) & 63))
@@ -560,6 +577,7 @@ static __device__ ExtRes extend_wave_pkl(const DevIndex& ix, const MemOpt& opt, 
         int m, mj, h1, h1i;
         if (beg < i - w) beg = i - w;
         if (end > i + w + 1) end = i + w + 1;
+        end = wave_uni(end);                               // (or the two minima become one three-operand vector instruction)
         if (end > qlen) end = qlen;
         if (beg == 0) { h1i = h0 - (o_del + e_del * (i + 1)); if (h1i < 0) h1i = 0; }
         else h1i = 0;
@@ -634,14 +652,11 @@ static __device__ ExtRes extend_wave_pkl(const DevIndex& ix, const MemOpt& opt, 
         if (m == 0) break;
         if (m > max) {
             max = m; max_i = i; max_j = mj;
-            int d = mj - i; d = d < 0 ? -d : d;
+            int d = mj - i; d = wave_uni(d < 0 ? -d : d);   // (as above: no three-operand vector maximum)
             max_off = max_off > d ? max_off : d;
-        } else if (zdrop > 0) {
-            if (i - max_i > mj - max_j) {
-                if (max - m - ((i - max_i) - (mj - max_j)) * e_del > zdrop) break;
-            } else {
-                if (max - m - ((mj - max_j) - (i - max_i)) * e_ins > zdrop) break;
-            }
+        } else if (zdrop > 0) {                            // (one test for both sides of the diagonal: fewer scalar branches)
+            const int dd = (i - max_i) - (mj - max_j);
+            if (max - m - ((dd > 0 ? dd : 0) * e_del + (dd < 0 ? -dd : 0) * e_ins) > zdrop) break;
         }
         {   // shrink the window to the non-zero span of the row just written
             int nb = end, jl = -2;
@@ -706,21 +721,11 @@ static __device__ ExtRes extend_wave_pkl(const DevIndex& ix, const MemOpt& opt, 
 // matters (the diagonal is inside any band) and the window always contains column i (its predecessor is alive).  The z-drop
 // rule can only fire on the diagonal itself (i - max_i == mj - max_j): if it would, the certificate is refused and the
 // DP runs.  Independent of w, so the caller's band-doubling loop sees the same score twice and stops, as it would.
-static __device__ inline int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-static __device__ inline int wave_prefix_sum(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) { const int u = __shfl_up(v, o); if (lane >= o) v += u; }
-    return v;
-}
 static __device__ bool extend_diag(const DevIndex& ix, const MemOpt& opt, const uint8_t* query, int lane,
                                    int qlen, int q0, int qstep, int tlen, int64_t t0, int tstep, int zdrop, int h0, ExtRes& r)
 {
+    qlen = wave_uni(qlen); q0 = wave_uni(q0); qstep = wave_uni(qstep); tlen = wave_uni(tlen); t0 = wave_uni64(t0); tstep = wave_uni(tstep);
+    zdrop = wave_uni(zdrop); h0 = wave_uni(h0);
     if (tlen < qlen || qlen <= 0 || h0 <= 0) return false;
     const int mx = score_max(opt);
     const int oe_del = opt.o_del + opt.e_del, oe_ins = opt.o_ins + opt.e_ins;
@@ -736,16 +741,16 @@ static __device__ bool extend_diag(const DevIndex& ix, const MemOpt& opt, const 
             score_lane(ST, query[q0 + qstep * j], p, n);
             s = score_at(p, n, ref_base2(ix, t0 + (int64_t)tstep * j));
         }
-        deficit += wave_sum(act ? mx - s : 0);
+        deficit += wave_sum_u(act ? mx - s : 0);
         if (deficit >= g1 || deficit >= h0) return false;
-        const int P = run + wave_prefix_sum(s, lane);                 // P_j (lanes past the query repeat the last one)
-        const int pm = wave_prefix_max(act ? P : NEG_INF_I32, lane);
-        int before = __shfl_up(pm, 1);                                // the maximum before row j: h0, earlier chunks, earlier lanes
+        const int P = run + dpp_prefix_sum(s);                        // P_j (lanes past the query repeat the last one)
+        const int pm = dpp_prefix_max(act ? P : NEG_INF_I32, NEG_INF_I32);
+        int before = dpp_shr1(pm, NEG_INF_I32);                       // the maximum before row j: h0, earlier chunks, earlier lanes
         if (lane == 0 || before < max) before = max;
         if (zdrop > 0 && wave_any(act && P <= before && before - P > zdrop)) return false;
-        const int cm = wave_max(act ? P : NEG_INF_I32);
+        const int cm = wave_bcast_u(pm, WAVE - 1);                    // the chunk's maximum: the last lane of its prefix maximum
         if (cm > max) { max = cm; max_i = c + __ffsll((long long)wave_ballot(act && P == cm)) - 1; }
-        run = wave_bcast(P, WAVE - 1);
+        run = wave_bcast_u(P, WAVE - 1);
     }
     r.score = max; r.qle = max_i + 1; r.tle = max_i + 1; r.gtle = qlen; r.gscore = run; r.max_off = 0;
     return true;
@@ -793,10 +798,13 @@ static __host__ __device__ inline int extend_ring(const MemOpt& opt, int max_len
 // HBM = true: reads whose rows do not fit a CU's LDS -- a bounded grid walks the reads and each workgroup keeps its rows in
 // its own slice of tv.dp_rows (global memory; only the read itself stays in LDS).  Same code, same results, slower rows.
 template <bool HBM, bool SHORT = false>
-static __device__ __forceinline__ void extend_read(const DevIndex& ix, const MemOpt& opt, const TileView& tv, int32_t* smem, const int r, const int lane)
+static __device__ __forceinline__ void extend_read(const DevIndex& ix, const MemOpt& opt, const TileView& tv, int32_t* smem, const int r_, const int lane)
 {
-    const int64_t s0 = tv.seed_off[r];
-    const int l_query = (int)(tv.seq_off[r + 1] - tv.seq_off[r] - 1);
+    // one wavefront, one read: everything that steers the loops below is wave-uniform, and is kept scalar (wave_ops.h: wave_uni).
+    // What is only stored (most of AlnReg a) stays in vector registers on purpose: the kernel is short of scalar ones
+    const int r = wave_uni(r_);
+    const int64_t s0 = wave_uni64(tv.seed_off[r]);
+    const int l_query = wave_uni((int)(tv.seq_off[r + 1] - tv.seq_off[r] - 1));
     const int cap = tv.max_len + 2;
     ExtLds L;
     uint8_t* sq;
@@ -814,7 +822,7 @@ static __device__ __forceinline__ void extend_read(const DevIndex& ix, const Mem
     for (int j = lane; j < l_query; j += WAVE) sq[j] = tv.seq[tv.seq_off[r] + j];
     __syncthreads();
 
-    const int n_chn = tv.n_chains[r];
+    const int n_chn = wave_uni(tv.n_chains[r]);
     const Chain* chains = tv.chains + s0;
     AlnReg* regs = tv.regs + s0;
     uint64_t* srt = tv.srt + s0;
@@ -824,7 +832,8 @@ static __device__ __forceinline__ void extend_read(const DevIndex& ix, const Mem
     const bool try_diag = !(tv.debug & 0x100);               // BWAMEM_HIP_DEBUGK=256: every extension through the DP (measurements, tests)
 
     for (int ci = 0; ci < n_chn; ++ci) {
-        const Chain c = chains[ci];
+        Chain c = chains[ci];
+        c.n = wave_uni(c.n); c.seed0 = wave_uni(c.seed0);
         const Seed* seeds = tv.cseeds + s0 + c.seed0;
         if (c.n == 0) continue;
         int64_t rmax0 = l_pac << 1, rmax1 = 0;
@@ -837,11 +846,14 @@ static __device__ __forceinline__ void extend_read(const DevIndex& ix, const Mem
         }
         rmax0 = rmax0 > 0 ? rmax0 : 0;
         rmax1 = rmax1 < l_pac << 1 ? rmax1 : l_pac << 1;
+        rmax0 = wave_uni64(rmax0); rmax1 = wave_uni64(rmax1);
+        const int64_t rbeg0 = wave_uni64(seeds[0].rbeg);
         if (rmax0 < l_pac && l_pac < rmax1) {
-            if (seeds[0].rbeg < l_pac) rmax1 = l_pac;
+            if (rbeg0 < l_pac) rmax1 = l_pac;
             else rmax0 = l_pac;
         }
-        { int rid; bns_clamp(ix, rmax0, seeds[0].rbeg, rmax1, rid); }
+        { int rid; bns_clamp(ix, rmax0, rbeg0, rmax1, rid); }
+        rmax0 = wave_uni64(rmax0); rmax1 = wave_uni64(rmax1);
 
         if (lane == 0) {
             for (int i = 0; i < c.n; ++i) srt[i] = (uint64_t)(uint32_t)seeds[i].score << 32 | (uint32_t)i;
@@ -850,7 +862,8 @@ static __device__ __forceinline__ void extend_read(const DevIndex& ix, const Mem
         __syncthreads();
 
         for (int k = c.n - 1; k >= 0; --k) {
-            const Seed s = seeds[(uint32_t)srt[k]];
+            Seed s = seeds[wave_uni((uint32_t)srt[k])];
+            s.rbeg = wave_uni64(s.rbeg); s.qbeg = wave_uni(s.qbeg); s.len = wave_uni(s.len);
             int i = n_regs;
             // already covered by an earlier region?  Upstream walks the read's regions in order and stops at the first that
             // contains the seed near its own diagonal; a read in a repeat family has hundreds of regions by now, so the lanes
@@ -880,10 +893,13 @@ static __device__ __forceinline__ void extend_read(const DevIndex& ix, const Mem
                 const unsigned long long bal = wave_ballot(hit);
                 if (bal) { i = base + __ffsll((long long)bal) - 1; break; }
             }
+            i = wave_uni(i);
             if (i < n_regs) {
                 for (i = k + 1; i < c.n; ++i) {       // an overlapping off-diagonal seed forces extension
-                    if (srt[i] == 0) continue;
-                    const Seed t = seeds[(uint32_t)srt[i]];
+                    const uint64_t si = (uint64_t)wave_uni64((long long)srt[i]);
+                    if (si == 0) continue;
+                    Seed t = seeds[(uint32_t)si];
+                    t.rbeg = wave_uni64(t.rbeg); t.qbeg = wave_uni(t.qbeg); t.len = wave_uni(t.len);
                     if (t.len < s.len * .95) continue;
                     if (s.qbeg <= t.qbeg && s.qbeg + s.len - t.qbeg >= s.len >> 2 && t.qbeg - s.qbeg != t.rbeg - s.rbeg) break;
                     if (t.qbeg <= s.qbeg && t.qbeg + t.len - s.qbeg >= s.len >> 2 && s.qbeg - t.qbeg != s.rbeg - t.rbeg) break;
@@ -912,6 +928,7 @@ static __device__ __forceinline__ void extend_read(const DevIndex& ix, const Mem
                     aw0 = opt.w << i;
                     e = extend_any<SHORT>(ix, opt, L, lane, s.qbeg, s.qbeg - 1, -1, (int)tmp, s.rbeg - 1, -1,
                                     aw0, opt.pen_clip5, opt.zdrop, s.len * opt.a, n_cells, try_diag);
+                    e.score = wave_uni(e.score); e.max_off = wave_uni(e.max_off);
                     a.score = e.score;
                     if (a.score == prev || e.max_off < (aw0 >> 1) + (aw0 >> 2)) break;
                 }
@@ -933,6 +950,7 @@ static __device__ __forceinline__ void extend_read(const DevIndex& ix, const Mem
                     aw1 = opt.w << i;
                     e = extend_any<SHORT>(ix, opt, L, lane, l_query - qe, qe, 1, (int)(rmax1 - rmax0 - re), rmax0 + re, 1,
                                     aw1, opt.pen_clip3, opt.zdrop, sc0, n_cells, try_diag);
+                    e.score = wave_uni(e.score); e.max_off = wave_uni(e.max_off);
                     a.score = e.score;
                     if (a.score == prev || e.max_off < (aw1 >> 1) + (aw1 >> 2)) break;
                 }
