@@ -84,6 +84,31 @@ _lib.bwamem_hip_bgzf_inflate_device.restype = _vp
 _lib.bwamem_hip_bgzf_inflate_device.argtypes = [_vp, ctypes.c_char_p, _sz, ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_int64)]
 
 
+class _BamOptions(ctypes.Structure):
+    """bwamem_bam_options_t"""
+    _fields_ = [("size", _sz), ("rg_line", ctypes.c_char_p), ("sort", ctypes.c_int), ("mark_dup", ctypes.c_int), ("tags", ctypes.c_uint),
+                ("write_header", ctypes.c_int)]
+
+
+_lib.bwamem_hip_batch_set_tags.argtypes = [_vp, ctypes.c_uint]
+_lib.bwamem_hip_fastq_to_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.POINTER(_BamOptions), ctypes.c_int, ctypes.c_int,
+                                         ctypes.POINTER(_DupCounts)]
+_TAG_BITS = {"SA": 1, "MC": 2, "MQ": 4}
+
+
+def _tag_mask(tags):
+    """("SA", "MC", "MQ") -> BWAMEM_HIP_TAG_* OR-ed"""
+    if isinstance(tags, (str, bytes)):
+        tags = (tags,)
+    mask = 0
+    for t in tags:
+        t = t.decode() if isinstance(t, bytes) else t
+        if t not in _TAG_BITS:
+            raise ValueError("unknown tag %r: the optional tags are SA, MC and MQ" % (t,))
+        mask |= _TAG_BITS[t]
+    return mask
+
+
 def _taken(p, n):
     out = ctypes.string_at(p, n)
     _lib.jnibwa_free(p)
@@ -372,7 +397,7 @@ class BwaMemAligner:
             self.index.deRefIndex()
 
     def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False, sort=False, index_path=None, quals=None,
-                       read_group=None, mark_duplicates=False):
+                       read_group=None, mark_duplicates=False, tags=()):
         """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
         `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
         "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred).
@@ -383,18 +408,20 @@ class BwaMemAligner:
         quals: one Phred+33 string per sequence, each as long as its sequence: the records carry them as QUAL.  read_group: an
         "@RG\\tID:..." header line: it goes into the header, and every record carries RG:Z:<ID>.  Either implies device=True.
         mark_duplicates=True (needs device=True, sort=True, quals or read_group: the records have to stay on the device): duplicates
-        are marked on the device within this call before the sort (csrc/bam_dup.h), and the counts are returned as a dict."""
+        are marked on the device within this call before the sort (csrc/bam_dup.h), and the counts are returned as a dict.
+        tags: any of "SA", "MC", "MQ": the records carry them, built on the device (csrc/bam_encode.h); implies device=True."""
+        mask = _tag_mask(tags)
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
-        if mark_duplicates and not (device or sort or quals is not None or read_group is not None):
+        if mark_duplicates and not (device or sort or quals is not None or read_group is not None or mask):
             raise ValueError("mark_duplicates needs device=True or sort=True: the host-framing path takes the records off the device unmarked")
         opts = self._getOpts()
         seqs = [func(e) for e in sequences]
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
         if names is not None and len(names) != len(seqs):
             raise ValueError("%d names for %d sequences" % (len(names), len(seqs)))
-        if quals is not None or read_group is not None:
-            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group, mark_duplicates)
+        if quals is not None or read_group is not None or mask:
+            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group, mark_duplicates, mask)
         buf = struct.pack("=i", len(seqs)) + b"".join(s + b"\0" for s in seqs)
         arr = None
         if names is not None:
@@ -433,7 +460,7 @@ class BwaMemAligner:
             raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s" % (self.index.indexImageFile, path))
         return counts.as_dict() if mark_duplicates else None
 
-    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group, mark_duplicates=False):
+    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group, mark_duplicates=False, tag_mask=0):
         """alignSeqsToBam through the batch calls, which take qualities and a read group; nothing is written unless all of it succeeds"""
         if quals is not None:
             quals = [q.encode() if isinstance(q, str) else bytes(q) for q in quals]
@@ -464,6 +491,8 @@ class BwaMemAligner:
                     raise ValueError("the qualities were refused: every byte must be in 33..126")
             if rg is not None and _lib.bwamem_hip_batch_set_read_group(b, rg) != 0:
                 raise ValueError("the read group was refused: one '@RG\\t' line with an ID: field of 1..254 bytes")
+            if tag_mask and _lib.bwamem_hip_batch_set_tags(b, tag_mask) != 0:
+                raise fail
             if _lib.bwamem_hip_batch_keep_offsets(b, 1) != 0 or _lib.bwamem_hip_batch_align(idx, self._getOpts(), pb, b, 0) != 0:
                 raise fail
             counts = _DupCounts()
@@ -505,7 +534,7 @@ class BwaMemAligner:
                 f.write(bai)
         return counts.as_dict() if mark_duplicates else None
 
-    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False):
+    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False, tags=()):
         """Additive: FASTQ in, a BAM file out.  fastq1 / fastq2: FASTQ text (bytes), or the path of a FASTQ file (str); bytes or a
         file that begin with 1f 8b are compressed FASTQ and are handed over as they are: BGZF (bgzip) is inflated on the device, plain
         gzip on the host (csrc/bgzf_inflate.h);
@@ -513,7 +542,9 @@ class BwaMemAligner:
         alignPairs() -- interleaved pairs.  The text is taken apart on the device: the records carry the reads' names and base
         qualities, and RG:Z:<ID> when read_group (an "@RG\\tID:..." header line) is given.  sort / index_path as alignSeqsToBam.
         mark_duplicates=True: duplicates are marked on the device within this call, before the sort (csrc/bam_dup.h -- the highest
-        sum of base qualities keeps a group's place), and the counts are returned as a dict."""
+        sum of base qualities keeps a group's place), and the counts are returned as a dict.
+        tags: any of "SA", "MC", "MQ", as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam."""
+        mask = _tag_mask(tags)
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
         opts = self._getOpts()
@@ -533,7 +564,10 @@ class BwaMemAligner:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
             try:
-                if any(t is not None and t[:2] == b"\x1f\x8b" for t in (t1, t2)):
+                if mask:
+                    o = _BamOptions(size=ctypes.sizeof(_BamOptions), rg_line=rg, sort=1 if sort else 0, mark_dup=1 if mark_duplicates else 0, tags=mask, write_header=1)
+                    rc = _lib.bwamem_hip_fastq_to_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, ctypes.byref(o), fd, fd_bai, ctypes.byref(counts))
+                elif any(t is not None and t[:2] == b"\x1f\x8b" for t in (t1, t2)):
                     if not all(t is None or t[:2] == b"\x1f\x8b" for t in (t1, t2)):
                         raise ValueError("fastq1 and fastq2 must both be compressed or both be text")
                     rc = _lib.bwamem_hip_align_fastq_gz_to_marked_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, rg, 1 if sort else 0, fd, fd_bai, 1,

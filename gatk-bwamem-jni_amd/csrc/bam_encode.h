@@ -22,6 +22,19 @@
 //                    (bwamem_hip_batch_set_read_group) RG:Z:<ID> comes last on every record, unmapped ones included
 //   read names       the caller's (1..254 bytes each), else "r<index>" / "p<pair index>" with the index counted over the
 //                    whole logical call (read_id0 of the align call + the index within the batch)
+//   SA, MC, MQ       on request only (bwamem_hip_batch_set_tags; BAM_TAG_*), between XA and RG: NM MD AS XS XA SA MC MQ RG.  Like
+//                    everything above they are defined on the response alone.  For a read with records 0..n-1 in response order:
+//                    SA:Z goes on record k when k is mapped and has no 0x100 and at least one other record j of the read is
+//                    mapped and has no 0x100; its value is one entry "rname,pos,strand,CIGAR,mapQ,NM;" for each such j != k,
+//                    in response order: rname the contig's @SQ name, pos 1-based, strand + or - from j's 0x10, CIGAR j's response
+//                    words as text (clips stay S, whatever j's own line shows; "*" for none), mapQ and NM j's (mem_aln2sam's rule,
+//                    in the SAM tags specification's format).  Records with 0x100 carry no SA and are listed in none.
+//                    MC:Z / MQ:i exist only in a paired encode: they go on every record of read 2i / 2i+1, mapped or not, whose
+//                    mate's record 0 is mapped (the record the response's mate fields come from): MC is that record's CIGAR as
+//                    text (clips S), MQ its mapping quality in the smallest integer type.  An unpaired encode ignores both bits.
+//                    A record the tags push past 2^31 - 1 bytes is refused like any other (BAM_ERR_SPAN)
+// The text of other records does not fit bam_byte's shape (a pure function of record and position), so the tagged forms read it
+// from a per-read side buffer made by the same three steps as the records: sizes (BamTagInfo), a scan, and the text (bam_put_sa_entry, bam_put_cigar).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -61,6 +74,18 @@ BAM_HD int bam_int_width(int32_t v) { return v >= 0 ? (v <= 0xff ? 1 : v <= 0xff
 BAM_HD uint8_t bam_int_type(int32_t v) { const int w = bam_int_width(v); return (uint8_t)(v >= 0 ? (w == 1 ? 'C' : w == 2 ? 'S' : 'I') : (w == 1 ? 'c' : w == 2 ? 's' : 'i')); }
 
 BAM_HD int bam_dec_digits(uint64_t v) { int n = 1; while (v >= 10) { v /= 10; ++n; } return n; }
+// bytes of v's decimal text, and the text itself at dst: the digits come out of a register, last one first
+BAM_HD int bam_dec_len(int64_t v) { return v < 0 ? 1 + bam_dec_digits(0 - (uint64_t)v) : bam_dec_digits((uint64_t)v); }
+BAM_HD void bam_put_dec(uint8_t* dst, int64_t v)
+{
+    const int neg = v < 0, n = bam_dec_len(v);
+    uint64_t u = neg ? 0 - (uint64_t)v : (uint64_t)v;
+    if (neg) dst[0] = '-';
+    for (int d = n - 1; d >= neg; --d) { dst[d] = (uint8_t)('0' + (int)(u % 10)); u /= 10; }
+}
+
+// the optional tags (bwamem_hip_batch_set_tags; the values of BWAMEM_HIP_TAG_*)
+enum { BAM_TAG_SA = 1, BAM_TAG_MC = 2, BAM_TAG_MQ = 4, BAM_TAG_ALL = 7 };
 
 // One response record (layout of jnibwa.c:43-98, as sam_writer.cpp walks it) and the layout of its BAM record.
 struct BamRec {
@@ -76,14 +101,24 @@ struct BamRec {
     int32_t o_cigar, o_seq, o_qual, o_nm, o_md, o_as, o_xs, o_xa, o_rg, total;
     // the read group's ID (null: no RG tag); bam_parse leaves none, bam_name sets the tile's
     const uint8_t* rg; int32_t l_rg;
+    // the tagged forms only (TAGS): the bytes of the CIGAR as text, and the values of SA and MC in the read's and its mate's side
+    // text (bam_tags sets them; a length of 0: no tag).  SA's value is sa[0, l_sa + sa_cut_len) without [sa_cut, sa_cut + sa_cut_len),
+    // the record's own entry
+    int32_t l_cigtxt;
+    const uint8_t* sa; const uint8_t* mc;
+    int32_t l_sa, sa_cut, sa_cut_len, l_mc, has_mq, mq;
+    int32_t o_sa, o_mc, o_mq;
 };
 
 // Parses the k-th record of a read (k counts from 0: later mapped records are hard-clipped) at p, of at most n_avail words; l_read =
 // the read's length.  n_seqs bounds the contig ids.  The name fields of R must be set by the caller before bam_layout.
-// -> 0, or BAM_ERR_* (R is then unusable).
+// -> 0, or BAM_ERR_* (R is then unusable).  TAGS: also the length of the CIGAR's text, and no SA / MC / MQ until bam_tags says so;
+// the forms without TAGS never touch those fields.
+template <bool TAGS = false>
 BAM_HD int bam_parse(const uint32_t* p, int64_t n_avail, int k, int32_t l_read, int32_t n_seqs, BamRec& R)
 {
     R.rg = 0; R.l_rg = 0;
+    if (TAGS) { R.l_cigtxt = 0; R.sa = R.mc = 0; R.l_sa = R.sa_cut = R.sa_cut_len = R.l_mc = R.has_mq = R.mq = 0; }
     if (n_avail < 1) return BAM_ERR_PARSE;
     const uint32_t fm = p[0];
     int64_t at = 1;
@@ -131,7 +166,9 @@ BAM_HD int bam_parse(const uint32_t* p, int64_t n_avail, int k, int32_t l_read, 
         const uint32_t v = R.cig[c], op = v & 0xf, len = v >> 4;
         if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += len;
         if (op == 4 || op == 5) { if (c == 0) clip5 = len; else clip3 = len; }
+        if (TAGS) R.l_cigtxt += bam_dec_digits(len) + 1;
     }
+    if (TAGS && R.n_cig == 0) R.l_cigtxt = 1;                            // "*" (at most 65 535 operations of 11 bytes: no overflow)
     if (R.refid < 0) R.bin = 4680;
     else if (!R.mapped) R.bin = bam_reg2bin(R.pos, (int64_t)R.pos + 1);
     else R.bin = bam_reg2bin(R.pos, (int64_t)R.pos + (span > 0 ? span : 1));
@@ -149,7 +186,8 @@ BAM_HD void bam_default_name(BamRec& R, int paired, uint64_t read_index)
     R.l_name = 1 + bam_dec_digits(R.name_idx);
 }
 
-// the section offsets and the total size (block_size included) of the record; needs the parse and the name
+// the section offsets and the total size (block_size included) of the record; needs the parse and the name (TAGS: and bam_tags)
+template <bool TAGS = false>
 BAM_HD int32_t bam_layout(BamRec& R)
 {
     int64_t o = 36 + (int64_t)R.l_name + 1;
@@ -161,6 +199,11 @@ BAM_HD int32_t bam_layout(BamRec& R)
     R.o_as = (int32_t)o;    if (R.mapped) o += 3 + bam_int_width(R.as);
     R.o_xs = (int32_t)o;    if (R.mapped && R.xs >= 0) o += 3 + bam_int_width(R.xs);
     R.o_xa = (int32_t)o;    if (R.mapped && R.n_xa > 0) o += 3 + (int64_t)R.n_xa + 1;
+    if (TAGS) {
+        R.o_sa = (int32_t)o; if (R.l_sa > 0) o += 3 + (int64_t)R.l_sa + 1;
+        R.o_mc = (int32_t)o; if (R.l_mc > 0) o += 3 + (int64_t)R.l_mc + 1;
+        R.o_mq = (int32_t)o; if (R.has_mq) o += 3 + bam_int_width(R.mq);
+    }
     R.o_rg = (int32_t)o;    if (R.rg) o += 3 + (int64_t)R.l_rg + 1;
     R.total = o > 0x7fffffff ? -1 : (int32_t)o;
     return R.total;
@@ -190,7 +233,16 @@ BAM_HD uint8_t bam_qual_byte(const BamRec& R, const uint8_t* qual, int32_t q)
     return (uint8_t)(qual[R.flag & 0x10 ? R.l_read - 1 - i : i] - 33);
 }
 
+// byte t of SA:Z: the side text without the record's own entry
+BAM_HD uint8_t bam_sa_tag_byte(const BamRec& R, int t)
+{
+    if (t < 3) return (uint8_t)(t == 0 ? 'S' : t == 1 ? 'A' : 'Z');
+    t -= 3;
+    return t >= R.l_sa ? (uint8_t)0 : R.sa[t < R.sa_cut ? t : t + R.sa_cut_len];
+}
+
 // the byte at position i (0 <= i < R.total) of the BAM record; qual = the read's qualities, or null (none: 0xFF)
+template <bool TAGS = false>
 BAM_HD uint8_t bam_byte(const BamRec& R, const uint8_t* raw, int32_t i, const uint8_t* qual = 0)
 {
     if (i < 36) {
@@ -232,6 +284,13 @@ BAM_HD uint8_t bam_byte(const BamRec& R, const uint8_t* raw, int32_t i, const ui
     if (i < R.o_as) return bam_str_tag_byte('M', 'D', R.md, R.n_md, i - R.o_md);
     if (i < R.o_xs) return bam_int_tag_byte('A', 'S', R.as, i - R.o_as);
     if (i < R.o_xa) return bam_int_tag_byte('X', 'S', R.xs, i - R.o_xs);
+    if (TAGS) {
+        if (i < R.o_sa) return bam_str_tag_byte('X', 'A', R.xa, R.n_xa, i - R.o_xa);
+        if (i < R.o_mc) return bam_sa_tag_byte(R, i - R.o_sa);
+        if (i < R.o_mq) return bam_str_tag_byte('M', 'C', R.mc, R.l_mc, i - R.o_mc);
+        if (i < R.o_rg) return bam_int_tag_byte('M', 'Q', R.mq, i - R.o_mq);
+        return bam_str_tag_byte('R', 'G', R.rg, R.l_rg, i - R.o_rg);
+    }
     if (i < R.o_rg) return bam_str_tag_byte('X', 'A', R.xa, R.n_xa, i - R.o_xa);
     return bam_str_tag_byte('R', 'G', R.rg, R.l_rg, i - R.o_rg);
 }
@@ -253,6 +312,11 @@ BAM_HD int bam_rg_id(const char* line, const char** id)
     return l_found;
 }
 
+// What a read contributes to the optional tags (k_bam_tag_size): record 0 as its mate sees it (0x100 | mapQ when mapped, else 0), and
+// the read's side text: the SA entries of its listed records back to back (l_sa bytes; 0 unless SA is asked for and n_sa >= 2), then
+// record 0's CIGAR as text (l_mc bytes; 0 unless the call is paired, MC is asked for and record 0 is mapped).
+struct BamTagInfo { int32_t mate, l_mc, n_sa, l_sa; };
+
 // What the size and emit kernels see of one tile of a batch (k_post.hip: launch_bam_size / launch_bam_emit).
 struct BamTile {
     const uint8_t* resp;          // the tile's packed response (TileOut.d)
@@ -271,6 +335,17 @@ struct BamTile {
     const int64_t* out_off;       // [n_reads + 1] their places in out (after the scan)
     uint8_t* out;
     int32_t* err;                 // BAM_ERR_* flags, OR-ed
+    // The tagged forms only (tags != 0).  These arrays span the batch and are indexed by read0 + r, so a read finds its mate's entry
+    // wherever the tiles were cut (a paired alignment never splits a pair -- plan_tiles and produce_streamed in pipeline.cpp -- but
+    // `paired` here is the encode call's own argument, so nothing is assumed).
+    uint32_t tags;                // BAM_TAG_*
+    int32_t read0, n_batch;       // the tile's first read within the batch, and the batch's reads
+    const int32_t* ctg_name_off;  // the contigs' names as in @SQ (DevIndex::ann_name_off / names: NUL-terminated, [n_seqs + 1] offsets)
+    const uint8_t* ctg_names;
+    BamTagInfo* tag_info;         // [n_batch]
+    int32_t* tag_sizes;           // [n_batch] bytes of each read's side text
+    const int64_t* tag_off;       // [n_batch + 1] their places in tag_text (after the scan)
+    uint8_t* tag_text;            // null in the size kernels
 };
 
 // names the record of read r of the tile
@@ -279,4 +354,67 @@ BAM_HD void bam_name(const BamTile& t, int r, BamRec& R)
     if (t.names) { R.name = t.names + t.name_off[r]; R.l_name = (int32_t)(t.name_off[r + 1] - t.name_off[r]); R.name_idx = 0; R.name_letter = 0; }
     else bam_default_name(R, t.paired, (uint64_t)(t.read_index0 + r));
     R.rg = t.rg; R.l_rg = t.l_rg;
+}
+
+// ---- SA / MC / MQ (the rule at the top).  A record is listed in SA when it is mapped and not secondary.
+BAM_HD bool bam_sa_listed(const BamRec& R) { return R.mapped && !(R.flag & 0x100); }
+BAM_HD int32_t bam_ctg_name_len(const BamTile& t, int32_t rid) { return t.ctg_name_off[rid + 1] - t.ctg_name_off[rid] - 1; }
+// bytes of R's entry "rname,pos,strand,CIGAR,mapQ,NM;" (R parsed with TAGS)
+BAM_HD int64_t bam_sa_entry_len(const BamTile& t, const BamRec& R)
+{
+    return (int64_t)bam_ctg_name_len(t, R.refid) + 1 + bam_dec_len((int64_t)R.pos + 1) + 3 + (int64_t)R.l_cigtxt + 1 + bam_dec_len(R.mapq) + 1 + bam_dec_len(R.nm) + 1;
+}
+BAM_HD uint8_t bam_cigar_letter(uint32_t op) { return op < 8 ? (uint8_t)(0x3d5048534e44494dull >> (8 * op)) : op == 8 ? (uint8_t)'X' : (uint8_t)'?'; }   // "MIDNSHP=" X
+
+// R's CIGAR as text (l_cigtxt bytes; clips as the response has them: S) at dst.  Lane sub of G writes operations sub, sub + G, ...;
+// every lane adds up the places itself, as every lane parses the record itself.
+BAM_HD void bam_put_cigar(uint8_t* dst, const BamRec& R, int sub, int G)
+{
+    if (R.n_cig == 0) { if (sub == 0) dst[0] = '*'; return; }
+    int64_t o = 0;
+    for (int32_t c = 0; c < R.n_cig; ++c) {
+        const uint32_t v = R.cig[c], len = v >> 4;
+        const int nd = bam_dec_digits(len);
+        if (c % G == sub) { bam_put_dec(dst + o, len); dst[o + nd] = bam_cigar_letter(v & 0xf); }
+        o += nd + 1;
+    }
+}
+// R's SA entry (bam_sa_entry_len bytes) at dst, by lane sub of G
+BAM_HD void bam_put_sa_entry(uint8_t* dst, const BamTile& t, const BamRec& R, int sub, int G)
+{
+    const uint8_t* rname = t.ctg_names + t.ctg_name_off[R.refid];
+    const int32_t l_rname = bam_ctg_name_len(t, R.refid);
+    for (int32_t i = sub; i < l_rname; i += G) dst[i] = rname[i];
+    int64_t o = l_rname;
+    const int n_pos = bam_dec_len((int64_t)R.pos + 1);
+    if (sub == 0) { dst[o] = ','; bam_put_dec(dst + o + 1, (int64_t)R.pos + 1); dst[o + 1 + n_pos] = ','; dst[o + 2 + n_pos] = R.flag & 0x10 ? '-' : '+'; dst[o + 3 + n_pos] = ','; }
+    o += n_pos + 4;
+    bam_put_cigar(dst + o, R, sub, G);
+    o += R.l_cigtxt;
+    if (sub == G - 1) {
+        const int n_q = bam_dec_len(R.mapq);
+        dst[o] = ','; bam_put_dec(dst + o + 1, R.mapq); dst[o + 1 + n_q] = ','; bam_put_dec(dst + o + 2 + n_q, R.nm); dst[o + 2 + n_q + bam_dec_len(R.nm)] = ';';
+    }
+}
+
+// SA, MC and MQ of record R (parsed with TAGS) of the tile's read r, before bam_layout.  sa_at: the bytes of the read's listed records
+// before R.  -> the bytes of R's own entry (0: not listed), for the caller to add to sa_at.
+BAM_HD int64_t bam_tags(const BamTile& t, int r, BamRec& R, int64_t sa_at)
+{
+    const int64_t g = (int64_t)t.read0 + r;
+    int64_t own = 0;
+    if (bam_sa_listed(R)) {
+        own = bam_sa_entry_len(t, R);
+        const int32_t l_all = t.tag_info[g].l_sa;
+        if (l_all > 0) { R.l_sa = (int32_t)(l_all - own); R.sa_cut = (int32_t)sa_at; R.sa_cut_len = (int32_t)own; if (t.tag_text) R.sa = t.tag_text + t.tag_off[g]; }
+    }
+    const int64_t m = g ^ 1;
+    if (t.paired && (t.tags & (BAM_TAG_MC | BAM_TAG_MQ)) && m < t.n_batch) {
+        const BamTagInfo mate = t.tag_info[m];
+        if (mate.mate & 0x100) {
+            if (t.tags & BAM_TAG_MC) { R.l_mc = mate.l_mc; if (t.tag_text) R.mc = t.tag_text + t.tag_off[m] + mate.l_sa; }
+            if (t.tags & BAM_TAG_MQ) { R.has_mq = 1; R.mq = mate.mate & 0xff; }
+        }
+    }
+    return own;
 }

@@ -130,7 +130,9 @@ __global__ void k_pack(TileView tv, uint8_t* dst)
 
 // ------------------------------------------------------------------ BAM records from the packed response (bam_encode.h)
 // Three steps like k_final_se / launch_scan / k_pack: the bytes of every read's records, a scan, and the records themselves.
-// step 1: one lane per read walks the read's response records and adds up the sizes of their BAM records
+// step 1: one lane per read walks the read's response records and adds up the sizes of their BAM records.  TAGS: with the optional
+// tags, whose sizes come from the reads' BamTagInfo (k_bam_tag_size of every tile has run, and the scan of the side texts)
+template <bool TAGS>
 __global__ void __launch_bounds__(64) k_bam_size(BamTile t)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -143,14 +145,15 @@ __global__ void __launch_bounds__(64) k_bam_size(BamTile t)
         const int64_t n = (hi - lo) >> 2;
         const int32_t l_read = (int32_t)(t.raw_off[r + 1] - t.raw_off[r] - 1);
         const int32_t n_aln = (int32_t)p[0];
-        int64_t at = 1;
+        int64_t at = 1, sa_at = 0;
         if (n_aln < 0 || l_read < 0 || ((hi - lo) & 3)) err = BAM_ERR_PARSE;
         for (int32_t k = 0; k < n_aln && !err; ++k) {
             BamRec R;
-            err = bam_parse(p + at, n - at, k, l_read, t.n_seqs, R);
+            err = bam_parse<TAGS>(p + at, n - at, k, l_read, t.n_seqs, R);
             if (err) break;
             bam_name(t, r, R);
-            if (bam_layout(R) < 0) { err = BAM_ERR_SPAN; break; }
+            if (TAGS) sa_at += bam_tags(t, r, R, sa_at);
+            if (bam_layout<TAGS>(R) < 0) { err = BAM_ERR_SPAN; break; }
             total += R.total; at += R.words;
         }
         if (!err && at != n) err = BAM_ERR_PARSE;
@@ -160,11 +163,76 @@ __global__ void __launch_bounds__(64) k_bam_size(BamTile t)
     if (err) atomicOr(t.err, err);
 }
 
+// The side text of the optional tags (bam_encode.h: BamTagInfo), by the same three steps.  Step 1, one lane per read: what the read's
+// text will hold.  A read whose response does not parse gets no text; k_bam_size meets the same error and flags it.
+__global__ void __launch_bounds__(64) k_bam_tag_size(BamTile t)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= t.n_reads) return;
+    const int64_t lo = t.resp_off[r], hi = t.resp_off[r + 1];
+    BamTagInfo info; info.mate = info.l_mc = info.n_sa = info.l_sa = 0;
+    int64_t l_sa = 0;
+    int err = 0;
+    if (hi > lo) {
+        const uint32_t* p = (const uint32_t*)(t.resp + lo);
+        const int64_t n = (hi - lo) >> 2;
+        const int32_t l_read = (int32_t)(t.raw_off[r + 1] - t.raw_off[r] - 1);
+        const int32_t n_aln = (int32_t)p[0];
+        int64_t at = 1;
+        if (n_aln < 0 || l_read < 0 || ((hi - lo) & 3)) err = BAM_ERR_PARSE;
+        for (int32_t k = 0; k < n_aln && !err; ++k) {
+            BamRec R;
+            err = bam_parse<true>(p + at, n - at, k, l_read, t.n_seqs, R);
+            if (err) break;
+            if (bam_sa_listed(R)) { ++info.n_sa; l_sa += bam_sa_entry_len(t, R); }
+            if (k == 0 && R.mapped) { info.mate = 0x100 | R.mapq; if (t.paired && (t.tags & BAM_TAG_MC)) info.l_mc = R.l_cigtxt; }
+            at += R.words;
+        }
+        if (!err && l_sa + info.l_mc > 0x7fffffff) err = BAM_ERR_SPAN;
+    }
+    if (err) { info.mate = info.l_mc = info.n_sa = 0; l_sa = 0; if (err == BAM_ERR_SPAN) atomicOr(t.err, err); }
+    if ((t.tags & BAM_TAG_SA) && info.n_sa >= 2) info.l_sa = (int32_t)l_sa;
+    t.tag_info[t.read0 + r] = info;
+    t.tag_sizes[t.read0 + r] = info.l_sa + info.l_mc;
+}
+
+// step 3, by the lane groups of k_bam_emit: the entries of the read's listed records, then record 0's CIGAR.  Nothing is written
+// outside the bytes step 1 counted.
+template <int G>
+__global__ void __launch_bounds__(256) k_bam_tag_text(BamTile t)
+{
+    const int r = blockIdx.x * (256 / G) + ((int)threadIdx.x / G), sub = (int)threadIdx.x % G;
+    if (r >= t.n_reads) return;
+    const int64_t g = (int64_t)t.read0 + r;
+    const BamTagInfo info = t.tag_info[g];
+    const int64_t lo = t.resp_off[r], hi = t.resp_off[r + 1];
+    if (hi <= lo || info.l_sa + info.l_mc <= 0 || t.tag_off[g + 1] - t.tag_off[g] != (int64_t)info.l_sa + info.l_mc) return;
+    uint8_t* dst = t.tag_text + t.tag_off[g];
+    const uint32_t* p = (const uint32_t*)(t.resp + lo);
+    const int64_t n = (hi - lo) >> 2;
+    const int32_t l_read = (int32_t)(t.raw_off[r + 1] - t.raw_off[r] - 1);
+    const int32_t n_aln = (int32_t)p[0];
+    int64_t at = 1, o = 0;
+    for (int32_t k = 0; k < n_aln; ++k) {
+        BamRec R;
+        if (bam_parse<true>(p + at, n - at, k, l_read, t.n_seqs, R)) return;
+        if (k == 0 && info.l_mc > 0 && R.mapped && R.l_cigtxt == info.l_mc) bam_put_cigar(dst + info.l_sa, R, sub, G);
+        if (info.l_sa > 0 && bam_sa_listed(R)) {
+            const int64_t len = bam_sa_entry_len(t, R);
+            if (o + len > info.l_sa) return;
+            bam_put_sa_entry(dst + o, t, R, sub, G);
+            o += len;
+        }
+        at += R.words;
+    }
+}
+
 // step 3: G lanes per read (8, or the wavefront for tiles of long reads) write the read's records.  Every lane parses the record
 // (the same few words for all of them); the lanes then share out the aligned 32-bit words of the record's span in the output,
 // each assembled in a register from bam_byte and stored whole.  Only the up to three bytes before the first aligned word
 // and after the last are stored singly.  Q: the batch carries qualities (the instantiation without them has no load for QUAL).
-template <int G, bool Q>
+// TAGS: SA / MC / MQ are asked for; their text comes from the side buffer (k_bam_tag_text) through the same word assembly.
+template <int G, bool Q, bool TAGS>
 __global__ void __launch_bounds__(256) k_bam_emit(BamTile t)
 {
     const int r = blockIdx.x * (256 / G) + ((int)threadIdx.x / G), sub = (int)threadIdx.x % G;
@@ -179,22 +247,26 @@ __global__ void __launch_bounds__(256) k_bam_emit(BamTile t)
     const uint8_t* qual = Q ? t.qual + t.raw_off[r] : nullptr;
     const int32_t l_read = (int32_t)(t.raw_off[r + 1] - t.raw_off[r] - 1);
     const int32_t n_aln = (int32_t)p[0];
-    int64_t at = 1;
+    int64_t at = 1, sa_at = 0;
     for (int32_t k = 0; k < n_aln; ++k) {
         BamRec R;
-        int err = bam_parse(p + at, n - at, k, l_read, t.n_seqs, R);
-        if (!err) { bam_name(t, r, R); if (bam_layout(R) < 0 || o + R.total > o_end) err = BAM_ERR_SPAN; }    // never outside the read's span
+        int err = bam_parse<TAGS>(p + at, n - at, k, l_read, t.n_seqs, R);
+        if (!err) {
+            bam_name(t, r, R);
+            if (TAGS) sa_at += bam_tags(t, r, R, sa_at);
+            if (bam_layout<TAGS>(R) < 0 || o + R.total > o_end) err = BAM_ERR_SPAN;                            // never outside the read's span
+        }
         if (err) { if (sub == 0) atomicOr(t.err, err); return; }
         uint8_t* dst = t.out + o;
         const int32_t lead = (int32_t)((4 - (o & 3)) & 3), head = R.total < lead ? R.total : lead;
         const int32_t nw = (R.total - head) >> 2, tail = R.total - head - 4 * nw;
-        if (sub < head) dst[sub] = bam_byte(R, raw, sub, qual);
+        if (sub < head) dst[sub] = bam_byte<TAGS>(R, raw, sub, qual);
         uint32_t* dw = (uint32_t*)(dst + head);
         for (int32_t w = sub; w < nw; w += G) {
             const int32_t i = head + 4 * w;
-            dw[w] = (uint32_t)bam_byte(R, raw, i, qual) | (uint32_t)bam_byte(R, raw, i + 1, qual) << 8 | (uint32_t)bam_byte(R, raw, i + 2, qual) << 16 | (uint32_t)bam_byte(R, raw, i + 3, qual) << 24;
+            dw[w] = (uint32_t)bam_byte<TAGS>(R, raw, i, qual) | (uint32_t)bam_byte<TAGS>(R, raw, i + 1, qual) << 8 | (uint32_t)bam_byte<TAGS>(R, raw, i + 2, qual) << 16 | (uint32_t)bam_byte<TAGS>(R, raw, i + 3, qual) << 24;
         }
-        if (sub < tail) dst[head + 4 * nw + sub] = bam_byte(R, raw, head + 4 * nw + sub, qual);
+        if (sub < tail) dst[head + 4 * nw + sub] = bam_byte<TAGS>(R, raw, head + 4 * nw + sub, qual);
         o += R.total; at += R.words;
     }
 }
@@ -1406,16 +1478,33 @@ void launch_bgzf_inflate(hipStream_t st, const uint8_t* comp, const BgzfMember* 
 void launch_bam_size(hipStream_t st, const BamTile& t)
 {
     if (t.n_reads <= 0) return;
-    hipLaunchKernelGGL(k_bam_size, dim3((t.n_reads + 63) / 64), dim3(64), 0, st, t);
+    if (t.tags) hipLaunchKernelGGL(k_bam_size<true>, dim3((t.n_reads + 63) / 64), dim3(64), 0, st, t);
+    else hipLaunchKernelGGL(k_bam_size<false>, dim3((t.n_reads + 63) / 64), dim3(64), 0, st, t);
+}
+template <bool TAGS>
+static void launch_bam_emit_t(hipStream_t st, const BamTile& t)
+{
+    if (t.max_len > 1000) {                                          // long reads: a wavefront per read
+        if (t.qual) hipLaunchKernelGGL((k_bam_emit<64, true, TAGS>), dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((k_bam_emit<64, false, TAGS>), dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);
+    } else if (t.qual) hipLaunchKernelGGL((k_bam_emit<8, true, TAGS>), dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
+    else hipLaunchKernelGGL((k_bam_emit<8, false, TAGS>), dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
 }
 void launch_bam_emit(hipStream_t st, const BamTile& t)
 {
     if (t.n_reads <= 0) return;
-    if (t.max_len > 1000) {                                          // long reads: a wavefront per read
-        if (t.qual) hipLaunchKernelGGL((k_bam_emit<64, true>), dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);
-        else hipLaunchKernelGGL((k_bam_emit<64, false>), dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);
-    } else if (t.qual) hipLaunchKernelGGL((k_bam_emit<8, true>), dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
-    else hipLaunchKernelGGL((k_bam_emit<8, false>), dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
+    if (t.tags) launch_bam_emit_t<true>(st, t); else launch_bam_emit_t<false>(st, t);
+}
+void launch_bam_tag_size(hipStream_t st, const BamTile& t)
+{
+    if (t.n_reads <= 0) return;
+    hipLaunchKernelGGL(k_bam_tag_size, dim3((t.n_reads + 63) / 64), dim3(64), 0, st, t);
+}
+void launch_bam_tag_text(hipStream_t st, const BamTile& t)
+{
+    if (t.n_reads <= 0) return;
+    if (t.max_len > 1000) hipLaunchKernelGGL(k_bam_tag_text<64>, dim3((t.n_reads + 3) / 4), dim3(256), 0, st, t);
+    else hipLaunchKernelGGL(k_bam_tag_text<8>, dim3((t.n_reads + 31) / 32), dim3(256), 0, st, t);
 }
 
 void launch_qual_check(hipStream_t st, const uint8_t* raw, const uint8_t* qual, const int64_t* raw_off, int n_reads, int32_t* err)

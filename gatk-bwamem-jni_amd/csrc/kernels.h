@@ -43,6 +43,10 @@ void launch_pack(hipStream_t st, const TileView& tv, uint8_t* dst);
 // BAM records of a tile's packed response (bam_encode.h): sizes per read, then -- after a launch_scan over the batch -- the records
 void launch_bam_size(hipStream_t st, const BamTile& t);
 void launch_bam_emit(hipStream_t st, const BamTile& t);
+// With t.tags, both take the tagged forms, and the side text of SA / MC / MQ is made first: _tag_size for every tile of the batch
+// (BamTagInfo and bytes per read), a launch_scan over the batch, then launch_bam_size; and _tag_text before launch_bam_emit
+void launch_bam_tag_size(hipStream_t st, const BamTile& t);
+void launch_bam_tag_text(hipStream_t st, const BamTile& t);
 // Qualities and names of a batch: the qualities against the reads (a NUL where the read's is, else 33..126), and the names of the
 // two reads of every pair against each other.  err: one int, zeroed by the caller; FASTQ_NO_ERROR - the smallest offending read
 void launch_qual_check(hipStream_t st, const uint8_t* raw, const uint8_t* qual, const int64_t* raw_off, int n_reads, int32_t* err);

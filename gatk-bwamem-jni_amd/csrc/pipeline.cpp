@@ -381,6 +381,9 @@ struct bwamem_batch_s {
     DevBuf d_qual, own_names, own_name_off, d_rg;
     bool has_qual = false, has_names = false;
     std::string rg_line, rg_id;                      // rg_id empty: no read group
+    // the optional tags of the records (bwamem_hip_batch_set_tags, BAM_TAG_*) and their side text (bam_encode.h: BamTagInfo)
+    unsigned tags = 0;
+    DevBuf tag_info, tag_sizes, tag_off, tag_scan_tmp, tag_text;
 };
 
 static const int LOG_TAB_N = 1 << 20;
@@ -1793,6 +1796,12 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
     HIP_OK(hipMemsetAsync(b->bam_sizes.p, 0, n * 4, ws.stream));       // reads no tile covers have no record
     HIP_OK(hipMemsetAsync(b->bam_err.p, 0, 64, ws.stream));
     const bool own_names = !names && b->has_names;                     // a batch made from FASTQ text: its own names
+    const unsigned tags = b->tags & (paired ? (unsigned)BAM_TAG_ALL : (unsigned)BAM_TAG_SA);      // an unpaired encode has no mates
+    if (tags) {
+        if (!(b->tag_info.ensure(n * sizeof(BamTagInfo)) && b->tag_sizes.ensure(n * 4) && b->tag_off.ensure((n + 1) * 8) && b->tag_scan_tmp.ensure(scan_tmp_bytes((int64_t)n + 1)))) return false;
+        HIP_OK(hipMemsetAsync(b->tag_info.p, 0, n * sizeof(BamTagInfo), ws.stream));                // reads no tile covers: no mapped record, no text
+        HIP_OK(hipMemsetAsync(b->tag_sizes.p, 0, n * 4, ws.stream));
+    }
     if (own_names && paired) launch_mate_names(ws.stream, b->own_names.as<uint8_t>(), b->own_name_off.as<int64_t>(), (int)(n >> 1), b->bam_err.as<int32_t>() + 1);
     std::vector<BamTile> tiles;
     for (const TileOut& to : b->tiles) {
@@ -1808,21 +1817,35 @@ static bool encode_bam(bwamem_batch_s* b, int paired, const char* names, const i
         if (b->has_qual) t.qual = b->d_qual.as<uint8_t>();
         if (!b->rg_id.empty()) { t.rg = b->d_rg.as<uint8_t>(); t.l_rg = (int32_t)b->rg_id.size(); }
         t.sizes = b->bam_sizes.as<int32_t>() + r0; t.out_off = b->bam_off.as<int64_t>() + r0; t.out = nullptr; t.err = b->bam_err.as<int32_t>();
+        if (tags) {
+            t.tags = tags; t.read0 = (int32_t)r0; t.n_batch = (int32_t)n;
+            t.ctg_name_off = ix->d.ann_name_off; t.ctg_names = (const uint8_t*)ix->d.names;
+            t.tag_info = b->tag_info.as<BamTagInfo>(); t.tag_sizes = b->tag_sizes.as<int32_t>(); t.tag_off = b->tag_off.as<int64_t>(); t.tag_text = nullptr;
+        }
         tiles.push_back(t);
+    }
+    if (tags) {                                                        // every tile's entries before any size: a mate may sit in another tile
+        for (const BamTile& t : tiles) launch_bam_tag_size(ws.stream, t);
+        launch_scan(ws.stream, b->tag_sizes.as<int32_t>(), b->tag_off.as<int64_t>(), (int)n, b->tag_scan_tmp.as<int64_t>());
     }
     for (const BamTile& t : tiles) launch_bam_size(ws.stream, t);
     launch_scan(ws.stream, b->bam_sizes.as<int32_t>(), b->bam_off.as<int64_t>(), (int)n, b->bam_scan_tmp.as<int64_t>());
     HIP_OK(hipGetLastError());
-    int64_t total = 0; int32_t errs[2] = { 0, 0 };                     // [1]: the mate-name check
+    int64_t total = 0, tag_total = 0; int32_t errs[2] = { 0, 0 };      // [1]: the mate-name check
     HIP_OK(hipMemcpyAsync(&total, b->bam_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, ws.stream));
+    if (tags) HIP_OK(hipMemcpyAsync(&tag_total, b->tag_off.as<int64_t>() + n, 8, hipMemcpyDeviceToHost, ws.stream));    // the same wait
     HIP_OK(hipMemcpyAsync(errs, b->bam_err.p, own_names && paired ? 8 : 4, hipMemcpyDeviceToHost, ws.stream));
     HIP_OK(hipStreamSynchronize(ws.stream));
     int32_t err = errs[0]; const int32_t mate_err = errs[1];
     if (mate_err) { fprintf(stderr, "[bwamem_hip] encode_bam: reads %d and %d are a pair but their names differ\n", FASTQ_NO_ERROR - mate_err, FASTQ_NO_ERROR - mate_err + 1); return false; }
     if (err & BAM_ERR_CIGAR_OPS) { fprintf(stderr, "[bwamem_hip] encode_bam: a record has more than %d CIGAR operations (not representable without the CG tag)\n", BAM_MAX_CIGAR_OPS); return false; }
-    if (err || total < 0) { fprintf(stderr, "[bwamem_hip] encode_bam: the resident response does not parse (flags %d)\n", err); return false; }
+    if (err || total < 0 || tag_total < 0) { fprintf(stderr, "[bwamem_hip] encode_bam: the resident response does not parse (flags %d)\n", err); return false; }
     if (total == 0) { b->bam_encoded = true; return true; }
     if (!b->bam.ensure((size_t)total)) return false;
+    if (tags) {
+        if (!b->tag_text.ensure((size_t)tag_total + 8)) return false;
+        for (BamTile& t : tiles) { t.tag_text = b->tag_text.as<uint8_t>(); launch_bam_tag_text(ws.stream, t); }
+    }
     for (BamTile& t : tiles) { t.out = b->bam.as<uint8_t>(); launch_bam_emit(ws.stream, t); }
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(&err, b->bam_err.p, 4, hipMemcpyDeviceToHost, ws.stream));
@@ -1866,6 +1889,13 @@ static bool set_read_group(bwamem_batch_s* b, const char* rg_line)
     if (!b->d_rg.ensure(256)) return false;
     HIP_OK(hipMemcpy(b->d_rg.p, id, (size_t)l_id, hipMemcpyHostToDevice));
     b->rg_line = rg_line; b->rg_id.assign(id, (size_t)l_id);
+    return true;
+}
+
+static bool set_tags(bwamem_batch_s* b, unsigned mask)
+{
+    if (mask & ~(unsigned)BAM_TAG_ALL) { fprintf(stderr, "[bwamem_hip] set_tags: unknown bits 0x%x (SA = 1, MC = 2, MQ = 4)\n", mask & ~(unsigned)BAM_TAG_ALL); return false; }
+    b->tags = mask;
     return true;
 }
 
@@ -1990,6 +2020,15 @@ int bwamem_hip_batch_set_read_group(bwamem_batch_t* b, const char* rg_line)
         std::lock_guard<std::mutex> lk(b->idx->mu);
         if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
         return set_read_group(b, rg_line) ? 0 : -1;
+    });
+}
+
+int bwamem_hip_batch_set_tags(bwamem_batch_t* b, unsigned mask)
+{
+    return guarded("bwamem_hip_batch_set_tags", -1, [&]() -> int {
+        if (!b || !b->idx) return -1;
+        std::lock_guard<std::mutex> lk(b->idx->mu);
+        return set_tags(b, mask) ? 0 : -1;
     });
 }
 

@@ -253,9 +253,61 @@ char* bwamem_hip_sam_header(bwaidx_t* idx, size_t* pBytes)
     } catch (...) { return 0; }
 }
 
-// quals: the reads' Phred+33 strings back to back, NUL-terminated like the request's reads, or null; rg_id: a read group's ID, or null
+}  // extern "C"
+
+namespace {
+
+// What SA / MC / MQ need of one read (the rule at the top of bam_encode.h), taken from the response by a walk of its own: the SA
+// entry of every record ("" for records that are unmapped or secondary), and record 0 as the mate sees it.
+struct ReadTags { std::vector<std::string> sa; bool mapped0 = false; int mapq0 = 0; std::string cigar0; };
+
+bool response_tags(const uint8_t* p, const uint8_t* end, uint32_t n_reads, int paired, const std::vector<ContigInfo>& contigs, std::vector<ReadTags>& out)
+{
+    static const char OPS[] = "MIDNSHP=X";
+    out.assign(n_reads, ReadTags());
+    for (uint32_t r = 0; r < n_reads; ++r) {
+        if (paired && (n_reads & 1u) && r == n_reads - 1) continue;
+        if (p + 4 > end) return false;
+        const int32_t n_aln = rd32(p);
+        for (int32_t k = 0; k < n_aln; ++k) {
+            if (p + 4 > end) return false;
+            const int32_t fm = rd32(p);
+            const int flag = (fm >> 16) & 0xffff;
+            std::string entry;
+            if (!(flag & 4)) {
+                if (p + 24 > end) return false;
+                const int32_t rid = rd32(p), pos = rd32(p), nm = rd32(p);
+                p += 8;
+                const int32_t n_cig = rd32(p);
+                if (rid < 0 || rid >= (int32_t)contigs.size() || n_cig < 0 || p + 4 * (size_t)n_cig + 4 > end) return false;
+                std::string cigar;
+                for (int32_t c = 0; c < n_cig; ++c) { const uint32_t v = (uint32_t)rd32(p); cigar += std::to_string(v >> 4); cigar += (v & 0xf) < 9 ? OPS[v & 0xf] : '?'; }
+                if (cigar.empty()) cigar = "*";
+                for (int s = 0; s < 2; ++s) {                           // MD, XA
+                    if (p + 4 > end) return false;
+                    const int32_t l = rd32(p);
+                    if (l < 0 || p + ((l + 3) & ~3) > end) return false;
+                    p += (l + 3) & ~3;
+                }
+                if (!(flag & 0x100))
+                    entry = contigs[rid].name + "," + std::to_string((long long)pos + 1) + "," + (flag & 0x10 ? "-" : "+") + "," + cigar + "," + std::to_string(fm & 0xff) + "," + std::to_string(nm) + ";";
+                if (k == 0) { out[r].mapped0 = true; out[r].mapq0 = fm & 0xff; out[r].cigar0 = cigar; }
+            }
+            if ((flag & 9) == 1) { if (p + 12 > end) return false; p += 12; }
+            out[r].sa.push_back(entry);
+        }
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// quals: the reads' Phred+33 strings back to back, NUL-terminated like the request's reads, or null; rg_id: a read group's ID, or null;
+// tags: BAM_TAG_* (SA / MC / MQ after XA)
 static char* response_to_sam(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired,
-                             const char* quals, const char* rg_id, size_t* pBytes)
+                             const char* quals, const char* rg_id, size_t* pBytes, unsigned tags = 0)
 {
     if (pBytes) *pBytes = 0;
     if (!idx || !pSeq || !response) return 0;
@@ -269,6 +321,10 @@ static char* response_to_sam(bwaidx_t* idx, const char* pSeq, const void* respon
         Out o;
         o.s.reserve(responseBytes * 4 + (size_t)n_reads * 64);
         static const char OPS[] = "MIDNSHP=X";
+        if (tags & ~(unsigned)BAM_TAG_ALL) return 0;
+        if (!paired) tags &= BAM_TAG_SA;
+        std::vector<ReadTags> rt;
+        if (tags && !response_tags(p, end, n_reads, paired, contigs, rt)) return 0;
         for (uint32_t r = 0; r < n_reads; ++r) {
             const size_t l_seq = strlen(q);
             const char* seq = q;
@@ -343,6 +399,15 @@ static char* response_to_sam(bwaidx_t* idx, const char* pSeq, const void* respon
                     if (xs >= 0) { o.put("\tXS:i:"); o.num(xs); }
                     if (!xa.empty()) { o.put("\tXA:Z:"); o.put(xa); }
                 }
+                if ((tags & BAM_TAG_SA) && !rt[r].sa[(size_t)k].empty()) {
+                    std::string others;
+                    for (size_t j = 0; j < rt[r].sa.size(); ++j) if (j != (size_t)k) others += rt[r].sa[j];
+                    if (!others.empty()) { o.put("\tSA:Z:"); o.put(others); }
+                }
+                if ((tags & (BAM_TAG_MC | BAM_TAG_MQ)) && (r ^ 1u) < n_reads && rt[r ^ 1u].mapped0) {
+                    if (tags & BAM_TAG_MC) { o.put("\tMC:Z:"); o.put(rt[r ^ 1u].cigar0); }
+                    if (tags & BAM_TAG_MQ) { o.put("\tMQ:i:"); o.num(rt[r ^ 1u].mapq0); }
+                }
                 if (rg_id) { o.put("\tRG:Z:"); o.put(rg_id); }
                 o.ch('\n');
             }
@@ -365,6 +430,12 @@ char* bwamem_hip_response_to_sam_q(bwaidx_t* idx, const char* pSeq, const void* 
                                    const char* quals, const char* rgId, size_t* pBytes)
 {
     return response_to_sam(idx, pSeq, response, responseBytes, readNames, paired, quals, rgId, pBytes);
+}
+
+char* bwamem_hip_response_to_sam_tags(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired,
+                                      const char* quals, const char* rgId, unsigned tags, size_t* pBytes)
+{
+    return response_to_sam(idx, pSeq, response, responseBytes, readNames, paired, quals, rgId, pBytes, tags);
 }
 
 // header text with the read group's line after the last @SQ line; false: the line is refused
@@ -579,8 +650,9 @@ namespace {
 // totals, or null), sort if asked, compress, index if asked (fd_bai >= 0), write.  The header carries rg_line when there is one.
 // Everything is made before the first byte is written.
 int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off, const char* rg_line, int mark_dup,
-                      bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header)
+                      bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, unsigned tags = 0)
 {
+    if (tags && bwamem_hip_batch_set_tags(b, tags) != 0) return -1;
     if (bwamem_hip_batch_encode_bam(b, paired, names, name_off) != 0) return -1;
     if (mark_dup && bwamem_hip_batch_mark_duplicates(b, paired, counts) != 0) return -1;
     if (sort && bwamem_hip_batch_sort_bam(b) != 0) return -1;
@@ -633,7 +705,7 @@ int request_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, c
 }
 
 int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
-                      const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, bool gz = false)
+                      const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, bool gz = false, unsigned tags = 0)
 {
     try {
         if (!idx || !opt || fd < 0) return -1;
@@ -646,7 +718,7 @@ int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, con
         if (!bo.b) return -1;
         if (rg_line && bwamem_hip_batch_set_read_group(bo.b, rg_line) != 0) return -1;
         if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
-        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, mark_dup, counts, sort, fd, fd_bai, write_header);
+        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, mark_dup, counts, sort, fd, fd_bai, write_header, tags);
     } catch (...) { return -1; }
 }
 
@@ -693,6 +765,26 @@ int bwamem_hip_align_fastq_gz_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt,
     if (counts) memset(counts, 0, sizeof *counts);
     return fastq_to_bam_file("align_fastq_gz_to_marked_bam", idx, opt, pes, (const char*)gz1, n1, (const char*)gz2, n2, rg_line, mark_dup != 0, mark_dup ? counts : nullptr,
                              sort, fd, fd_bai, write_header, true);
+}
+
+// The one-call entry point with its choices in a struct: bwamem_hip_align_fastq_gz_to_marked_bam / _fastq_to_marked_bam by the first
+// two bytes of the input, plus the optional tags.  Fields beyond o->size are zero.
+int bwamem_hip_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
+                            const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts)
+{
+    if (counts) memset(counts, 0, sizeof *counts);
+    bwamem_bam_options_t v;
+    memset(&v, 0, sizeof v);
+    if (o) {
+        if (o->size < sizeof(size_t) || o->size > sizeof v) { fprintf(stderr, "[bwamem_hip] fastq_to_bam: options of %zu bytes (this library knows %zu)\n", o->size, sizeof v); return -1; }
+        memcpy(&v, o, o->size);
+    }
+    if (v.tags & ~(unsigned)BAM_TAG_ALL) { fprintf(stderr, "[bwamem_hip] fastq_to_bam: unknown tag bits 0x%x\n", v.tags & ~(unsigned)BAM_TAG_ALL); return -1; }
+    auto is_gz = [](const void* p, size_t n) { return p && n >= 2 && ((const uint8_t*)p)[0] == 0x1f && ((const uint8_t*)p)[1] == 0x8b; };
+    const bool gz = is_gz(in1, n1);
+    if (in2 && n2 && is_gz(in2, n2) != gz) { fprintf(stderr, "[bwamem_hip] fastq_to_bam: one input is compressed and the other is not\n"); return -1; }
+    return fastq_to_bam_file("fastq_to_bam", idx, opt, pes, (const char*)in1, n1, (const char*)in2, n2, v.rg_line, v.mark_dup != 0, v.mark_dup ? counts : nullptr,
+                             v.sort != 0, fd, fd_bai, v.write_header, gz, v.tags);
 }
 
 }  // extern "C"

@@ -272,6 +272,37 @@ int    bwamem_hip_align_fastq_gz_to_marked_bam(bwaidx_t* idx, const mem_opt_t* o
                                                size_t n2, const char* rg_line, int sort, int fd, int fd_bai, int write_header, int mark_dup,
                                                bwamem_dup_counts_t* counts);
 
+/* SA, MC and MQ tags, built on the device (csrc/bam_encode.h, "SA, MC, MQ"; additive and off by default: with no tag asked for
+ * every entry point above produces byte for byte what it did).  SA:Z links the records of a chimeric read; MC:Z and MQ:i are the
+ * mate's CIGAR and mapping quality, what samtools fixmate adds.  All three are defined on the response alone.  The text of other
+ * records comes from a per-read side buffer that kernels next to the encoder fill (sizes, a scan, the text) from the resident
+ * response and the index's contig names, so the tags cost no transfer and no host pass; the tag order on a record is
+ * NM MD AS XS XA SA MC MQ RG.  Mark-duplicates, the sort, the compressor and the index see larger records and nothing else.
+ *   _set_tags       before _encode_bam: mask = BWAMEM_HIP_TAG_* OR-ed; 0 removes the tags.  Unknown bits: non-zero with a message,
+ *                   and the batch keeps the mask it had.  A new alignment keeps the mask, as it keeps the read group.  MC and MQ
+ *                   need the mate, so an unpaired _encode_bam ignores those two bits.
+ *   bwamem_hip_response_to_sam_tags   bwamem_hip_response_to_sam_q plus the tags named by `tags`, written by host code of its own from
+ *                   the response.  A BAM record decodes to exactly this line, SA, MC and MQ included.
+ *   bwamem_hip_fastq_to_bam   the one-call entry point with its choices in a struct: plain or compressed FASTQ (a stream that begins
+ *                   with 1f 8b is taken as compressed: BGZF or plain gzip as for _upload_fastq_gz) through align, encode with
+ *                   o->tags, mark (o->mark_dup; counts as for bwamem_hip_align_fastq_gz_to_marked_bam), sort (o->sort), compress and
+ *                   index on the device (fd_bai >= 0 needs sort and write_header).  o->size = sizeof(bwamem_bam_options_t) as the
+ *                   caller compiled it: fields beyond it take their zero defaults, and a size this library does not know is
+ *                   refused.  o == NULL: every field zero. */
+enum { BWAMEM_HIP_TAG_SA = 1, BWAMEM_HIP_TAG_MC = 2, BWAMEM_HIP_TAG_MQ = 4 };
+typedef struct {
+    size_t size;                /* sizeof(bwamem_bam_options_t) */
+    const char* rg_line;        /* as for _set_read_group, or NULL */
+    int sort, mark_dup;
+    unsigned tags;              /* BWAMEM_HIP_TAG_* */
+    int write_header;
+} bwamem_bam_options_t;
+int    bwamem_hip_batch_set_tags(bwamem_batch_t* b, unsigned mask);
+char*  bwamem_hip_response_to_sam_tags(bwaidx_t* idx, const char* pSeq, const void* response, size_t responseBytes, const char* const* readNames, int paired,
+                                       const char* quals, const char* rgId, unsigned tags, size_t* pBytes);
+int    bwamem_hip_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
+                               const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
