@@ -95,6 +95,32 @@ _lib.bwamem_hip_fastq_to_bam.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ct
                                          ctypes.POINTER(_DupCounts)]
 _TAG_BITS = {"SA": 1, "MC": 2, "MQ": 4}
 
+_QC_PAIRS = ("total", "primary", "secondary", "supplementary", "duplicates", "primary_duplicates", "mapped", "primary_mapped", "paired", "read1", "read2",
+             "properly_paired", "both_mapped", "singletons", "mate_diff_chr", "mate_diff_chr_mapq5")
+_QC_SINGLES = ("unplaced", "sequences", "total_length", "max_length", "reads_mq0", "bases_mapped", "bases_mapped_cigar", "bases_soft_clipped", "ins_events",
+               "ins_bases", "del_events", "del_bases", "mismatches", "records_without_nm")
+_QC_ARRAYS = {"mapq_hist": 0, "qual_hist": 1, "isize_fr": 2, "isize_rf": 3, "isize_tandem": 4, "contig_mapped": 5, "contig_unmapped": 6}
+_QC_REPORTS = {"flagstat": 0, "idxstats": 1, "summary": 2, "insert_size": 3}
+
+
+class _QcCounts(ctypes.Structure):
+    """bwamem_qc_counts_t"""
+    _fields_ = ([(n, ctypes.c_uint64 * 2) for n in _QC_PAIRS] + [(n, ctypes.c_uint64) for n in _QC_SINGLES]
+                + [("isize_min", ctypes.c_uint64 * 3), ("isize_max", ctypes.c_uint64 * 3)])
+
+
+_lib.bwamem_hip_qc_create.restype = _vp; _lib.bwamem_hip_qc_create.argtypes = [_vp]
+_lib.bwamem_hip_qc_free.restype = None; _lib.bwamem_hip_qc_free.argtypes = [_vp]
+_lib.bwamem_hip_qc_add_batch.argtypes = [_vp, _vp]
+_lib.bwamem_hip_qc_add_records_device.argtypes = [_vp, ctypes.c_char_p, _sz]
+_lib.bwamem_hip_qc_counts.argtypes = [_vp, ctypes.POINTER(_QcCounts)]
+_lib.bwamem_hip_qc_array.restype = _i64; _lib.bwamem_hip_qc_array.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), _sz]
+_lib.bwamem_hip_qc_serialize.restype = _vp; _lib.bwamem_hip_qc_serialize.argtypes = [_vp, ctypes.POINTER(_sz)]
+_lib.bwamem_hip_qc_add_serialized.argtypes = [_vp, ctypes.c_char_p, _sz]
+_lib.bwamem_hip_qc_report.restype = _vp; _lib.bwamem_hip_qc_report.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(_sz)]
+_lib.bwamem_hip_fastq_to_bam_qc.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.POINTER(_BamOptions), ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(_DupCounts), _vp]
+
 
 def _tag_mask(tags):
     """("SA", "MC", "MQ") -> BWAMEM_HIP_TAG_* OR-ed"""
@@ -113,6 +139,79 @@ def _taken(p, n):
     out = ctypes.string_at(p, n)
     _lib.jnibwa_free(p)
     return out
+
+
+class BwaMemQc:
+    """Additive: an alignment-QC accumulator (csrc/bam_qc.h) -- flagstat, idxstats, summary numbers and insert sizes of the records
+    of any number of alignSeqsToBam / alignFastqToBam calls (qc=...), reduced on the device while the records are there.  The index
+    must stay open while batches are added."""
+
+    def __init__(self, index):
+        self.index = index
+        self._q = _lib.bwamem_hip_qc_create(index.refIndex())
+        index.deRefIndex()
+        if not self._q:
+            raise RuntimeError("Unable to create a QC accumulator for bwa-mem index %s" % index.indexImageFile)
+
+    def _ptr(self):
+        if not self._q:
+            raise RuntimeError("The QC accumulator has been closed.")
+        return self._q
+
+    def close(self):
+        if self._q:
+            _lib.bwamem_hip_qc_free(self._q)
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def counts(self):
+        """every counter by its name; the flagstat counters as (QC-passed, QC-failed), isize_min / isize_max as (FR, RF, TANDEM)"""
+        c = _QcCounts()
+        if _lib.bwamem_hip_qc_counts(self._ptr(), ctypes.byref(c)) != 0:
+            raise RuntimeError("bwamem_hip_qc_counts failed")
+        out = {n: (int(getattr(c, n)[0]), int(getattr(c, n)[1])) for n in _QC_PAIRS}
+        out.update({n: int(getattr(c, n)) for n in _QC_SINGLES})
+        out["isize_min"], out["isize_max"] = tuple(int(x) for x in c.isize_min), tuple(int(x) for x in c.isize_max)
+        return out
+
+    def array(self, name):
+        """mapq_hist, qual_hist, isize_fr, isize_rf, isize_tandem, contig_mapped or contig_unmapped, as a list of ints"""
+        if name not in _QC_ARRAYS:
+            raise ValueError("unknown QC array %r: %s" % (name, ", ".join(sorted(_QC_ARRAYS))))
+        n = _lib.bwamem_hip_qc_array(self._ptr(), _QC_ARRAYS[name], None, 0)
+        buf = (ctypes.c_uint64 * max(n, 1))()
+        _lib.bwamem_hip_qc_array(self._ptr(), _QC_ARRAYS[name], buf, n)
+        return [int(x) for x in buf[:n]]
+
+    def _report(self, kind):
+        sz = ctypes.c_size_t()
+        p = _lib.bwamem_hip_qc_report(self._ptr(), _QC_REPORTS[kind], ctypes.byref(sz))
+        if not p:
+            raise RuntimeError("bwamem_hip_qc_report failed")
+        return _taken(p, sz.value).decode()
+
+    def flagstat(self): return self._report("flagstat")
+    def idxstats(self): return self._report("idxstats")
+    def summary(self): return self._report("summary")
+    def insertSizeMetrics(self): return self._report("insert_size")
+
+    def serialize(self):
+        sz = ctypes.c_size_t()
+        p = _lib.bwamem_hip_qc_serialize(self._ptr(), ctypes.byref(sz))
+        if not p:
+            raise RuntimeError("bwamem_hip_qc_serialize failed")
+        return _taken(p, sz.value)
+
+    def add(self, other):
+        """adds another accumulator, or the bytes of one (serialize(): other calls, devices, ranks); ValueError when it is of another index"""
+        blob = other.serialize() if isinstance(other, BwaMemQc) else bytes(other)
+        if _lib.bwamem_hip_qc_add_serialized(self._ptr(), blob, len(blob)) != 0:
+            raise ValueError("the QC blob was refused: another version, or an index with another number of contigs")
 
 
 class CouldNotReadImageException(RuntimeError):
@@ -382,6 +481,10 @@ class BwaMemAligner:
     def setProperPairEndStats(self, stats): self.pairEndStats = stats
     def getIndex(self): return self.index
 
+    def newQc(self):
+        """Additive: an empty QC accumulator (BwaMemQc) for this aligner's index, to be handed to alignSeqsToBam / alignFastqToBam"""
+        return BwaMemQc(self.index)
+
     def alignSeqsRaw(self, sequences, func=lambda s: s):
         """the raw native response (BwaMemAligner.java:192-214)"""
         opts = self._getOpts()
@@ -397,7 +500,7 @@ class BwaMemAligner:
             self.index.deRefIndex()
 
     def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False, sort=False, index_path=None, quals=None,
-                       read_group=None, mark_duplicates=False, tags=()):
+                       read_group=None, mark_duplicates=False, tags=(), qc=None):
         """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
         `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
         "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred).
@@ -409,19 +512,21 @@ class BwaMemAligner:
         "@RG\\tID:..." header line: it goes into the header, and every record carries RG:Z:<ID>.  Either implies device=True.
         mark_duplicates=True (needs device=True, sort=True, quals or read_group: the records have to stay on the device): duplicates
         are marked on the device within this call before the sort (csrc/bam_dup.h), and the counts are returned as a dict.
-        tags: any of "SA", "MC", "MQ": the records carry them, built on the device (csrc/bam_encode.h); implies device=True."""
+        tags: any of "SA", "MC", "MQ": the records carry them, built on the device (csrc/bam_encode.h); implies device=True.
+        qc: a BwaMemQc (newQc()): the records of this call are added to it on the device, after the marking and before the sort, once
+        the call has succeeded (csrc/bam_qc.h); accepted where mark_duplicates is."""
         mask = _tag_mask(tags)
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
-        if mark_duplicates and not (device or sort or quals is not None or read_group is not None or mask):
-            raise ValueError("mark_duplicates needs device=True or sort=True: the host-framing path takes the records off the device unmarked")
+        if (mark_duplicates or qc is not None) and not (device or sort or quals is not None or read_group is not None or mask):
+            raise ValueError("mark_duplicates and qc need device=True or sort=True: the host-framing path takes the records off the device unmarked")
         opts = self._getOpts()
         seqs = [func(e) for e in sequences]
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
         if names is not None and len(names) != len(seqs):
             raise ValueError("%d names for %d sequences" % (len(names), len(seqs)))
-        if quals is not None or read_group is not None or mask:
-            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group, mark_duplicates, mask)
+        if quals is not None or read_group is not None or mask or qc is not None:
+            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group, mark_duplicates, mask, qc)
         buf = struct.pack("=i", len(seqs)) + b"".join(s + b"\0" for s in seqs)
         arr = None
         if names is not None:
@@ -460,7 +565,7 @@ class BwaMemAligner:
             raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s" % (self.index.indexImageFile, path))
         return counts.as_dict() if mark_duplicates else None
 
-    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group, mark_duplicates=False, tag_mask=0):
+    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group, mark_duplicates=False, tag_mask=0, qc=None):
         """alignSeqsToBam through the batch calls, which take qualities and a read group; nothing is written unless all of it succeeds"""
         if quals is not None:
             quals = [q.encode() if isinstance(q, str) else bytes(q) for q in quals]
@@ -500,6 +605,13 @@ class BwaMemAligner:
                 raise fail
             if mark_duplicates and _lib.bwamem_hip_batch_mark_duplicates(b, paired, ctypes.byref(counts)) != 0:
                 raise fail
+            if qc is not None:                                          # into an accumulator of its own: qc takes it when the files are written
+                qc._ptr()
+                mine = BwaMemQc(self.index)
+                if _lib.bwamem_hip_qc_add_batch(mine._ptr(), b) != 0:
+                    raise fail
+                qc_blob = mine.serialize()
+                mine.close()
             if sort and _lib.bwamem_hip_batch_sort_bam(b) != 0:
                 raise fail
             sz = ctypes.c_size_t()
@@ -532,9 +644,11 @@ class BwaMemAligner:
         if bai is not None:
             with open(index_path, "wb") as f:
                 f.write(bai)
+        if qc is not None:
+            qc.add(qc_blob)
         return counts.as_dict() if mark_duplicates else None
 
-    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False, tags=()):
+    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False, tags=(), qc=None):
         """Additive: FASTQ in, a BAM file out.  fastq1 / fastq2: FASTQ text (bytes), or the path of a FASTQ file (str); bytes or a
         file that begin with 1f 8b are compressed FASTQ and are handed over as they are: BGZF (bgzip) is inflated on the device, plain
         gzip on the host (csrc/bgzf_inflate.h);
@@ -543,7 +657,8 @@ class BwaMemAligner:
         qualities, and RG:Z:<ID> when read_group (an "@RG\\tID:..." header line) is given.  sort / index_path as alignSeqsToBam.
         mark_duplicates=True: duplicates are marked on the device within this call, before the sort (csrc/bam_dup.h -- the highest
         sum of base qualities keeps a group's place), and the counts are returned as a dict.
-        tags: any of "SA", "MC", "MQ", as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam."""
+        tags: any of "SA", "MC", "MQ", as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam.
+        qc: a BwaMemQc, as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam_qc."""
         mask = _tag_mask(tags)
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
@@ -564,9 +679,10 @@ class BwaMemAligner:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
             try:
-                if mask:
+                if mask or qc is not None:
                     o = _BamOptions(size=ctypes.sizeof(_BamOptions), rg_line=rg, sort=1 if sort else 0, mark_dup=1 if mark_duplicates else 0, tags=mask, write_header=1)
-                    rc = _lib.bwamem_hip_fastq_to_bam(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, ctypes.byref(o), fd, fd_bai, ctypes.byref(counts))
+                    rc = _lib.bwamem_hip_fastq_to_bam_qc(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, ctypes.byref(o), fd, fd_bai, ctypes.byref(counts),
+                                                         qc._ptr() if qc is not None else None)
                 elif any(t is not None and t[:2] == b"\x1f\x8b" for t in (t1, t2)):
                     if not all(t is None or t[:2] == b"\x1f\x8b" for t in (t1, t2)):
                         raise ValueError("fastq1 and fastq2 must both be compressed or both be text")

@@ -1378,6 +1378,200 @@ __global__ void __launch_bounds__(64) k_dup_flags(DupView v)
     dup_wave_add(n_pair, &v.cnt[DUP_CNT_PAIR_DUP]);
 }
 
+// ------------------------------------------------------------------ alignment QC: a reduction over the records (bam_qc.h)
+#define QC_THREADS 256
+static __device__ inline unsigned long long qc_wave_sum(unsigned long long v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+static __device__ inline int qc_wave_max(int v)
+{
+    for (int o = 32; o > 0; o >>= 1) { const int u = __shfl_xor(v, o); v = u > v ? u : v; }
+    return v;
+}
+
+// (a) one lane per item (a read's records, or one record), a fixed grid striding over the items.  Per round every lane has at most
+// one record: the flag counters are ballots and popcounts kept by the lane whose number is the counter's word, the sums stay in the
+// lanes until the end, equal (refID, unmapped) are combined in the wave before one global add per distinct value, and mapq_hist and
+// the insert sizes below BAMQC_ISIZE_LDS go to the workgroup's copies in LDS.  Every wave runs its rounds in uniform control flow.
+__global__ void __launch_bounds__(QC_THREADS, 4) k_qc_records(QcView v)
+{
+    __shared__ unsigned long long s_cnt[2 * QC_F_N + QC_S_N];
+    __shared__ uint32_t s_mapq[BAMQC_MAPQ_BINS];
+    __shared__ uint32_t s_isize[QC_ORIENTATIONS * BAMQC_ISIZE_LDS];
+    __shared__ int32_t s_ext[2 * QC_ORIENTATIONS + 2];                 // the extremes as bam_qc.h encodes them, the longest read, the errors
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    for (int j = tid; j < 2 * QC_F_N + QC_S_N; j += QC_THREADS) s_cnt[j] = 0;
+    for (int j = tid; j < BAMQC_MAPQ_BINS; j += QC_THREADS) s_mapq[j] = 0;
+    for (int j = tid; j < QC_ORIENTATIONS * BAMQC_ISIZE_LDS; j += QC_THREADS) s_isize[j] = 0;
+    if (tid < 2 * QC_ORIENTATIONS + 2) s_ext[tid] = 0;
+    __syncthreads();
+    unsigned long long f_acc = 0, sums[QC_S_N];
+    for (int k = 0; k < QC_S_N; ++k) sums[k] = 0;
+    int32_t max_len = 0, err = 0, mn0 = 0, mn1 = 0, mn2 = 0, mx0 = 0, mx1 = 0, mx2 = 0;
+    const int64_t stride = (int64_t)gridDim.x * QC_THREADS;
+    for (int64_t base = (int64_t)blockIdx.x * QC_THREADS; base < v.n_items; base += stride) {
+        const int64_t i = base + tid;
+        int64_t o = 0, hi = 0;
+        if (i < v.n_items) { o = v.off[i]; hi = v.off[i + 1]; }
+        bool live = o < hi;
+        while (wave_any(live)) {
+            QcRec q = {};
+            bool ok = false;
+            if (live) {
+                int e = 0;
+                int64_t size = 0;
+                if (hi - o < BAMSORT_MIN_REC) e = BAMQC_ERR_WALK;
+                else {
+                    size = 4 + (int64_t)(int32_t)bamsort_ld32(v.bam + o);
+                    if (size < BAMSORT_MIN_REC || size > hi - o || (!v.grouped && size != hi - o)) e = BAMQC_ERR_WALK;
+                }
+                if (!e) e = qc_record(v.bam + o, size, v.n_contigs, q);
+                if (e) { err |= e; live = false; }
+                else { ok = true; o += size; live = o < hi; }
+            }
+            // the flag counters: word 2k + w
+            const uint32_t fm = ok ? q.fmask : 0u;
+            const bool w1 = ok && q.w != 0;
+            const bool any_w1 = wave_any(w1);
+#pragma unroll
+            for (int k = 0; k < QC_F_N; ++k) {
+                const bool bit = (fm >> k & 1u) != 0;
+                const int c0 = __popcll(wave_ballot_b(bit && !w1));
+                if (lane == 2 * k) f_acc += (unsigned long long)c0;
+                if (any_w1) {
+                    const int c1 = __popcll(wave_ballot_b(bit && w1));
+                    if (lane == 2 * k + 1) f_acc += (unsigned long long)c1;
+                }
+            }
+            // the contigs: one add per distinct (refID, unmapped) of the wave
+            const int32_t key = ok && q.refid >= 0 ? q.refid * 2 + ((fm >> QC_F_MAPPED & 1u) ? 0 : 1) : -1;
+            unsigned long long rem = wave_ballot_b(key >= 0);
+            while (rem) {
+                const int leader = __ffsll((long long)rem) - 1;
+                const int32_t k = wave_bcast(key, leader);
+                const unsigned long long same = wave_ballot_b(key == k);
+                if (lane == leader) atomicAdd(&v.blk[QC_W_CONTIG + k], (unsigned long long)__popcll(same));
+                rem &= ~same;
+            }
+            if (ok) {
+                if (q.refid < 0) sums[QC_S_UNPLACED] += 1;
+                if (q.primary) {
+                    sums[QC_S_SEQUENCES] += 1; sums[QC_S_TOTAL_LENGTH] += (unsigned long long)q.l_seq;
+                    if (q.l_seq > max_len) max_len = q.l_seq;
+                }
+                if (q.mapped_primary) {
+                    if (q.mapq == 0) sums[QC_S_READS_MQ0] += 1;
+                    sums[QC_S_BASES_MAPPED] += (unsigned long long)q.l_seq; sums[QC_S_BASES_MAPPED_CIGAR] += q.m_cigar; sums[QC_S_BASES_SOFT_CLIPPED] += q.soft;
+                    sums[QC_S_INS_EVENTS] += q.ins_ev; sums[QC_S_INS_BASES] += q.ins_b; sums[QC_S_DEL_EVENTS] += q.del_ev; sums[QC_S_DEL_BASES] += q.del_b;
+                    sums[QC_S_MISMATCHES] += q.nm; sums[QC_S_RECORDS_WITHOUT_NM] += q.no_nm ? 1 : 0;
+                    atomicAdd(&s_mapq[q.mapq], 1u);
+                }
+                if (q.orient >= 0) {
+                    if (q.x < BAMQC_ISIZE_LDS) atomicAdd(&s_isize[q.orient * BAMQC_ISIZE_LDS + (int)q.x], 1u);
+                    else atomicAdd(&v.blk[QC_W_ISIZE + q.orient * BAMQC_ISIZE_BINS + (q.x < BAMQC_ISIZE_BINS - 1 ? (int)q.x : BAMQC_ISIZE_BINS - 1)], 1ull);
+                    const int32_t en = qc_dev_min_enc(q.x), ex = qc_dev_max_enc(q.x);
+                    if (q.orient == QC_FR) { mn0 = en > mn0 ? en : mn0; mx0 = ex > mx0 ? ex : mx0; }
+                    else if (q.orient == QC_RF) { mn1 = en > mn1 ? en : mn1; mx1 = ex > mx1 ? ex : mx1; }
+                    else { mn2 = en > mn2 ? en : mn2; mx2 = ex > mx2 ? ex : mx2; }
+                }
+            }
+        }
+    }
+    // the wave's part into LDS, then the workgroup's into the block: one global add per non-zero word
+    if (lane < 2 * QC_F_N && f_acc) atomicAdd(&s_cnt[lane], f_acc);
+    for (int k = 0; k < QC_S_N; ++k) {
+        const unsigned long long t = qc_wave_sum(sums[k]);
+        if (lane == 0 && t) atomicAdd(&s_cnt[2 * QC_F_N + k], t);
+    }
+    mn0 = qc_wave_max(mn0); mn1 = qc_wave_max(mn1); mn2 = qc_wave_max(mn2);
+    mx0 = qc_wave_max(mx0); mx1 = qc_wave_max(mx1); mx2 = qc_wave_max(mx2);
+    max_len = qc_wave_max(max_len);
+    for (int o = 32; o > 0; o >>= 1) err |= __shfl_xor(err, o);
+    if (lane == 0) {
+        if (mn0) atomicMax(&s_ext[0], mn0);
+        if (mn1) atomicMax(&s_ext[1], mn1);
+        if (mn2) atomicMax(&s_ext[2], mn2);
+        if (mx0) atomicMax(&s_ext[3], mx0);
+        if (mx1) atomicMax(&s_ext[4], mx1);
+        if (mx2) atomicMax(&s_ext[5], mx2);
+        if (max_len) atomicMax(&s_ext[6], max_len);
+        if (err) atomicOr(&s_ext[7], err);
+    }
+    __syncthreads();
+    for (int j = tid; j < 2 * QC_F_N + QC_S_N; j += QC_THREADS) if (s_cnt[j]) atomicAdd(&v.blk[QC_W_FLAG + j], s_cnt[j]);
+    for (int j = tid; j < BAMQC_MAPQ_BINS; j += QC_THREADS) if (s_mapq[j]) atomicAdd(&v.blk[QC_W_MAPQ + j], (unsigned long long)s_mapq[j]);
+    for (int j = tid; j < QC_ORIENTATIONS * BAMQC_ISIZE_LDS; j += QC_THREADS)
+        if (s_isize[j]) atomicAdd(&v.blk[QC_W_ISIZE + (j / BAMQC_ISIZE_LDS) * BAMQC_ISIZE_BINS + j % BAMQC_ISIZE_LDS], (unsigned long long)s_isize[j]);
+    if (tid < 2 * QC_ORIENTATIONS && s_ext[tid]) atomicMax((int*)&v.blk[QC_W_ISIZE_MIN + tid], s_ext[tid]);      // (the low half of a little-endian word)
+    if (tid == 6 && s_ext[6]) atomicMax((int*)&v.blk[QC_W_SUM + QC_S_MAX_LENGTH], s_ext[6]);
+    if (tid == 7 && s_ext[7]) atomicOr((int*)&v.blk[QC_W_ERR], s_ext[7]);
+}
+
+// (b) qual_hist, by the lane groups of k_dup_scores: G lanes per item (8, or the wavefront for long reads).  The group walks its
+// item's records itself (a handful of loads of one cache line), and for every primary record with qualities shares out the aligned
+// 32-bit words of QUAL, the up to three bytes before the first and after the last going singly.  One copy of the histogram per wave
+// in LDS, flushed once per workgroup.  Runs after k_qc_records found no error, and still checks every bound itself.
+template <int G>
+__global__ void __launch_bounds__(QC_THREADS) k_qc_qual(QcView v)
+{
+    __shared__ unsigned long long s_q[QC_THREADS / 64][BAMQC_QUAL_BINS];
+    const int tid = (int)threadIdx.x, sub = tid % G, per = QC_THREADS / G;
+    for (int j = tid; j < (QC_THREADS / 64) * BAMQC_QUAL_BINS; j += QC_THREADS) s_q[j / BAMQC_QUAL_BINS][j % BAMQC_QUAL_BINS] = 0;
+    __syncthreads();
+    unsigned long long* const h = s_q[tid >> 6];
+    for (int64_t base = (int64_t)blockIdx.x * per; base < v.n_items; base += (int64_t)gridDim.x * per) {
+        const int64_t i = base + tid / G;
+        int64_t o = 0, hi = 0;
+        if (i < v.n_items) { o = v.off[i]; hi = v.off[i + 1]; }
+        while (hi - o >= BAMSORT_MIN_REC) {
+            const uint8_t* rec = v.bam + o;
+            const int64_t size = 4 + (int64_t)(int32_t)bamsort_ld32(rec);
+            if (size < BAMSORT_MIN_REC || size > hi - o) break;
+            const uint32_t f = qc_ld16(rec + 18);
+            const int32_t n = (int32_t)bamsort_ld32(rec + 20);
+            const int64_t qo = 36 + (int64_t)rec[12] + 4 * (int64_t)qc_ld16(rec + 16) + ((int64_t)n + 1) / 2;
+            if (!(f & 0x900) && n > 0 && qo + n <= size && rec[qo] != 0xff) {
+                const uint8_t* q = rec + qo;
+                const int32_t lead = (int32_t)((4 - ((uintptr_t)q & 3)) & 3), head = n < lead ? n : lead;
+                const int32_t nw = (n - head) >> 2, tail = n - head - 4 * nw;
+                if (sub < head) atomicAdd(&h[qc_qual_bin(q[sub])], 1ull);
+                const uint32_t* w = (const uint32_t*)(q + head);
+                for (int32_t k = sub; k < nw; k += G) {
+                    const uint32_t x = w[k];
+                    const uint32_t b0 = qc_qual_bin(x & 0xff), b1 = qc_qual_bin(x >> 8 & 0xff), b2 = qc_qual_bin(x >> 16 & 0xff), b3 = qc_qual_bin(x >> 24);
+                    if (b0 == b1 && b1 == b2 && b2 == b3) atomicAdd(&h[b0], 4ull);
+                    else { atomicAdd(&h[b0], 1ull); atomicAdd(&h[b1], 1ull); atomicAdd(&h[b2], 1ull); atomicAdd(&h[b3], 1ull); }
+                }
+                if (sub < tail) atomicAdd(&h[qc_qual_bin(q[head + 4 * nw + sub])], 1ull);
+            }
+            o += size;
+        }
+    }
+    __syncthreads();
+    if (tid < BAMQC_QUAL_BINS) {
+        unsigned long long t = 0;
+        for (int wv = 0; wv < QC_THREADS / 64; ++wv) t += s_q[wv][tid];
+        if (t) atomicAdd(&v.blk[QC_W_QUAL + tid], t);
+    }
+}
+
+static int qc_grid(int64_t n_blocks, int n_cu, int per_cu)
+{
+    const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * per_cu;
+    return (int)(n_blocks < 1 ? 1 : n_blocks < cap ? n_blocks : cap);
+}
+void launch_qc_records(hipStream_t st, const QcView& v, int n_cu)
+{
+    hipLaunchKernelGGL(k_qc_records, dim3(qc_grid(((int64_t)v.n_items + QC_THREADS - 1) / QC_THREADS, n_cu, 8)), dim3(QC_THREADS), 0, st, v);
+}
+void launch_qc_qual(hipStream_t st, const QcView& v, int max_len, int n_cu)
+{
+    if (max_len > 1000) hipLaunchKernelGGL(k_qc_qual<64>, dim3(qc_grid(((int64_t)v.n_items + 3) / 4, n_cu, 16)), dim3(QC_THREADS), 0, st, v);      // long reads: a wavefront per read
+    else hipLaunchKernelGGL(k_qc_qual<8>, dim3(qc_grid(((int64_t)v.n_items + 31) / 32, n_cu, 16)), dim3(QC_THREADS), 0, st, v);
+}
+
 void launch_dup_entries(hipStream_t st, const DupView& v)
 {
     hipLaunchKernelGGL(k_dup_entries, dim3((v.n_tmpl + 63) / 64), dim3(64), 0, st, v);

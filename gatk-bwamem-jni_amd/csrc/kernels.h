@@ -5,6 +5,7 @@
 #include "bam_encode.h"
 #include "bam_sort.h"
 #include "bam_dup.h"
+#include "bam_qc.h"
 #include "fastq_parse.h"
 #include "bgzf_inflate.h"
 
@@ -99,6 +100,11 @@ void launch_dup_score_keys(hipStream_t st, const DupView& v, uint64_t* frag_key,
 void launch_dup_gather(hipStream_t st, const uint64_t* src, const uint32_t* idx, int n, uint64_t* out);
 void launch_dup_decide(hipStream_t st, const uint64_t* keys, const uint32_t* idx, const uint64_t* second, int n, const uint8_t* is_paired, uint8_t* dup);
 void launch_dup_flags(hipStream_t st, const DupView& v);
+// Alignment QC (bam_qc.h): _records reduces everything but qual_hist into v.blk (zeroed by the caller) and leaves the errors in word
+// QC_W_ERR and the longest primary read in QC_W_SUM + QC_S_MAX_LENGTH; when there is no error _qual adds qual_hist (max_len: that
+// longest read).  Both run a fixed grid sized by the device's compute units.
+void launch_qc_records(hipStream_t st, const QcView& v, int n_cu);
+void launch_qc_qual(hipStream_t st, const QcView& v, int max_len, int n_cu);
 
 // paired-end path (k_pe.hip)
 void launch_pestat_cand(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv, int8_t* cand_dir, int64_t* cand_is);

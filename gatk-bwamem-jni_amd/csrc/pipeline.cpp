@@ -375,6 +375,7 @@ struct bwamem_batch_s {
     DevBuf bam2, rec_cnt, rec_first, rec_src, rec_size, rec_psize, rec_dst, rec_scan_tmp;
     SortBufs srt;
     DupBufs dup;                                     // bwamem_hip_batch_mark_duplicates
+    DevBuf qc_blk;                                   // the block a QC add of this batch reduces into (bwamem_hip_qc_add_batch)
     DevBuf bai_win_base, bai_win, bai_winv, bai_cnt, bai_start, bai_cid, bai_chunks;   // the index (bwamem_hip_batch_index_bam)
     // what the records take from outside the response: base qualities laid out like d_raw (bwamem_hip_batch_set_qualities, or the
     // FASTQ text), names of the batch's own (bwamem_hip_batch_upload_fastq) and the read group (bwamem_hip_batch_set_read_group)
@@ -2491,6 +2492,242 @@ int bwamem_hip_mark_duplicates_device(bwaidx_t* idx, void* records, size_t nByte
             return ok;
         };
         return run() ? 0 : -1;
+    });
+}
+
+// ---- alignment QC (bam_qc.h; kernels next to the duplicate kernels).  The accumulator keeps its totals in host memory, in the word
+// layout of the device's block with the six extremes as plain values: every add reduces into a zeroed block of its own on the
+// batch's device, and the host adds that block only when its error word is clear -- so a failed call changes nothing, and a handle
+// with several replicas, several devices and several processes (the serialized form) need nothing more.
+struct bwamem_qc_s {
+    bwaidx_s* idx = nullptr;
+    int32_t n_contigs = 0;
+    std::vector<std::string> names; std::vector<int64_t> lens;
+    mutable std::mutex mu;
+    std::vector<uint64_t> w;        // qc_words(n_contigs)
+};
+enum : uint64_t { QC_BLOB_MAGIC = 0x0043514d454d4142ull /* "BAMEMQC" */, QC_BLOB_VERSION = 1 };
+enum { QC_BLOB_HEAD = 4 };          // words before the block: magic, version, n_contigs, words of the block
+
+static void qc_clear(bwamem_qc_s* q)
+{
+    q->w.assign(qc_words(q->n_contigs), 0);
+    for (int o = 0; o < QC_ORIENTATIONS; ++o) q->w[QC_W_ISIZE_MIN + o] = 0xffffffffull;
+}
+// totals += blk; from_device: blk is a call's block as the kernels left it, else another accumulator's words
+static void qc_add_words(bwamem_qc_s* q, const uint64_t* blk, bool from_device)
+{
+    std::lock_guard<std::mutex> lk(q->mu);
+    const size_t n = q->w.size();
+    uint64_t mn[QC_ORIENTATIONS], mx[QC_ORIENTATIONS];
+    for (int o = 0; o < QC_ORIENTATIONS; ++o) {
+        mn[o] = blk[QC_W_ISIZE_MIN + o]; mx[o] = blk[QC_W_ISIZE_MAX + o];
+        if (from_device) {
+            uint64_t cnt = 0;
+            for (int v = 0; v < BAMQC_ISIZE_BINS; ++v) cnt += blk[QC_W_ISIZE + (size_t)o * BAMQC_ISIZE_BINS + v];
+            mn[o] = cnt ? qc_dev_min(mn[o]) : 0xffffffffull; mx[o] = cnt ? qc_dev_max(mx[o]) : 0;
+        }
+    }
+    const uint64_t max_len = std::max(q->w[QC_W_SUM + QC_S_MAX_LENGTH], blk[QC_W_SUM + QC_S_MAX_LENGTH]);
+    for (size_t i = QC_W_FLAG; i < (size_t)QC_W_ISIZE_MIN; ++i) q->w[i] += blk[i];
+    q->w[QC_W_SUM + QC_S_MAX_LENGTH] = max_len;
+    for (int o = 0; o < QC_ORIENTATIONS; ++o) {
+        q->w[QC_W_ISIZE_MIN + o] = std::min(q->w[QC_W_ISIZE_MIN + o], mn[o]);
+        q->w[QC_W_ISIZE_MAX + o] = std::max(q->w[QC_W_ISIZE_MAX + o], mx[o]);
+    }
+    for (size_t i = QC_W_MAPQ; i < n; ++i) q->w[i] += blk[i];
+}
+
+// The records at d_bam, n_items items at d_off (grouped: the reads' records; else one record each), reduced into out (qc_words).  The
+// device of ix is current and its lock held.  Two host waits: the errors with the longest read, and the block.
+static bool qc_reduce_device(bwaidx_s* ix, const uint8_t* d_bam, const int64_t* d_off, size_t n_items, bool grouped, int32_t n_contigs, DevBuf& blk, std::vector<uint64_t>& out)
+{
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    if (n_items >= 0x7fffffffu) { fprintf(stderr, "[bwamem_hip] qc: too many records\n"); return false; }
+    const size_t words = qc_words(n_contigs);
+    if (!blk.ensure(words * 8)) return false;
+    HIP_OK(hipMemsetAsync(blk.p, 0, words * 8, ws.stream));
+    QcView v; memset(&v, 0, sizeof v);
+    v.bam = d_bam; v.off = d_off; v.n_items = (int32_t)n_items; v.grouped = grouped ? 1 : 0; v.n_contigs = n_contigs; v.blk = blk.as<unsigned long long>();
+    TIMED(ws, K_OTHER, launch_qc_records(ws.stream, v, ix->d.n_cu));
+    HIP_OK(hipGetLastError());
+    uint64_t head[QC_W_MAPQ];
+    HIP_OK(hipMemcpyAsync(head, blk.p, sizeof head, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 1: the errors and the longest read
+    if (head[QC_W_ERR] & BAMQC_ERR_CONTIG) { fprintf(stderr, "[bwamem_hip] qc: a record names a contig the index does not have (%d contigs)\n", n_contigs); return false; }
+    if (head[QC_W_ERR]) { fprintf(stderr, "[bwamem_hip] qc: the records do not chain, or a record is shorter than its own fields (flags %d)\n", (int)head[QC_W_ERR]); return false; }
+    TIMED(ws, K_OTHER, launch_qc_qual(ws.stream, v, (int)std::min<uint64_t>(head[QC_W_SUM + QC_S_MAX_LENGTH], 0x7fffffff), ix->d.n_cu));
+    HIP_OK(hipGetLastError());
+    out.resize(words);
+    HIP_OK(hipMemcpyAsync(out.data(), blk.p, words * 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 2: the block
+    return true;
+}
+
+// the block of a batch's records (empty: the batch has none); 0 = ok.  Takes the lock of the batch's replica.
+static int qc_batch_block(bwamem_qc_s* q, bwamem_batch_s* b, std::vector<uint64_t>& out)
+{
+    out.clear();
+    if (!q || !b || !b->idx) return -1;
+    if ((size_t)q->n_contigs != b->idx->h.contigs.size()) { fprintf(stderr, "[bwamem_hip] qc_add_batch: the batch's index has %zu contigs, the QC object %d\n", b->idx->h.contigs.size(), q->n_contigs); return -1; }
+    std::lock_guard<std::mutex> lk(b->idx->mu);
+    if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+    if (!b->bam_encoded) { fprintf(stderr, "[bwamem_hip] qc_add_batch: the batch holds no encoded records (bwamem_hip_batch_encode_bam)\n"); return -1; }
+    if (b->n_reads == 0 || b->bam_bytes == 0 || (b->bam_sorted && b->bam_n_rec == 0)) return 0;
+    const bool ok = b->bam_sorted ? qc_reduce_device(b->idx, b->bam.as<uint8_t>(), b->rec_dst.as<int64_t>(), b->bam_n_rec, false, q->n_contigs, b->qc_blk, out)
+                                  : qc_reduce_device(b->idx, b->bam.as<uint8_t>(), b->bam_off.as<int64_t>(), b->n_reads, true, q->n_contigs, b->qc_blk, out);
+    timed_collect(b->idx->ws);
+    if (!ok) out.clear();
+    return ok ? 0 : -1;
+}
+
+// (sam_writer.cpp) the one-call entry point reduces after marking and adds only when the whole call has succeeded; the report writers
+// read the contig table.  *blk: malloc'ed words, or null for a batch without records.
+int bwamem_qc_batch_block(bwamem_qc_t* q, bwamem_batch_t* b, uint64_t** blk)
+{
+    *blk = nullptr;
+    return guarded("bwamem_hip_fastq_to_bam_qc", -1, [&]() -> int {
+        std::vector<uint64_t> out;
+        if (qc_batch_block(q, b, out) != 0) return -1;
+        if (out.empty()) return 0;
+        *blk = (uint64_t*)malloc(out.size() * 8);
+        if (!*blk) return -1;
+        memcpy(*blk, out.data(), out.size() * 8);
+        return 0;
+    });
+}
+void bwamem_qc_commit(bwamem_qc_t* q, const uint64_t* blk) { if (q && blk) qc_add_words(q, blk, true); }
+const char* bwamem_qc_contig(const bwamem_qc_t* q, int i, int64_t* len)
+{
+    if (!q || i < 0 || i >= q->n_contigs) return nullptr;
+    if (len) *len = q->lens[(size_t)i];
+    return q->names[(size_t)i].c_str();
+}
+
+bwamem_qc_t* bwamem_hip_qc_create(bwaidx_t* idx)
+{
+    return guarded("bwamem_hip_qc_create", (bwamem_qc_t*)nullptr, [&]() -> bwamem_qc_t* {
+        if (!idx || idx->h.contigs.size() >= ((size_t)1 << 30)) return nullptr;
+        std::unique_ptr<bwamem_qc_s> q(new bwamem_qc_s());
+        q->idx = idx; q->n_contigs = (int32_t)idx->h.contigs.size();
+        for (const ContigInfo& c : idx->h.contigs) { q->names.push_back(c.name); q->lens.push_back((int64_t)c.len); }
+        qc_clear(q.get());
+        return q.release();
+    });
+}
+void bwamem_hip_qc_free(bwamem_qc_t* q) { delete q; }
+
+int bwamem_hip_qc_add_batch(bwamem_qc_t* q, bwamem_batch_t* b)
+{
+    return guarded("bwamem_hip_qc_add_batch", -1, [&]() -> int {
+        std::vector<uint64_t> out;
+        if (qc_batch_block(q, b, out) != 0) return -1;
+        if (!out.empty()) qc_add_words(q, out.data(), true);
+        return 0;
+    });
+}
+
+int bwamem_hip_qc_add_records_device(bwamem_qc_t* q, const void* records, size_t nBytes)
+{
+    return guarded("bwamem_hip_qc_add_records_device", -1, [&]() -> int {
+        if (!q || !q->idx || (nBytes && !records) || nBytes >= ((size_t)1 << 40)) return -1;
+        if (nBytes == 0) return 0;
+        // the walk along block_size is the host's here: the stream carries no other index of its records
+        std::vector<int64_t> off;
+        const uint8_t* p = (const uint8_t*)records;
+        int64_t o = 0;
+        const int64_t hi = (int64_t)nBytes;
+        while (o < hi) {
+            int32_t bs = 0;
+            if (hi - o >= BAMSORT_MIN_REC) memcpy(&bs, p + o, 4);
+            const int64_t size = 4 + (int64_t)bs;
+            if (hi - o < BAMSORT_MIN_REC || size < BAMSORT_MIN_REC || size > hi - o) {
+                fprintf(stderr, "[bwamem_hip] qc_add_records_device: the records do not chain to the end of the stream (record %zu at byte %lld)\n", off.size(), (long long)o);
+                return -1;
+            }
+            off.push_back(o); o += size;
+        }
+        off.push_back(o);
+        const size_t n_rec = off.size() - 1;
+        bwaidx_s* ix = q->idx;
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (hipSetDevice(ix->device) != hipSuccess) return -1;
+        std::vector<uint64_t> out;
+        auto run = [&]() -> bool {
+            Workspace& ws = ix->ws;
+            if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+            DevBuf bam, d_off, blk;
+            if (!bam.ensure(nBytes + 8) || !d_off.ensure((n_rec + 1) * 8)) return false;
+            HIP_OK(hipMemcpyAsync(bam.p, records, nBytes, hipMemcpyHostToDevice, ws.stream));
+            HIP_OK(hipMemcpyAsync(d_off.p, off.data(), (n_rec + 1) * 8, hipMemcpyHostToDevice, ws.stream));
+            const bool ok = qc_reduce_device(ix, bam.as<uint8_t>(), d_off.as<int64_t>(), n_rec, false, q->n_contigs, blk, out);
+            HIP_OK(hipStreamSynchronize(ws.stream));
+            timed_collect(ws);
+            return ok;
+        };
+        if (!run()) return -1;
+        qc_add_words(q, out.data(), true);
+        return 0;
+    });
+}
+
+int bwamem_hip_qc_counts(const bwamem_qc_t* q, bwamem_qc_counts_t* out)
+{
+    if (!q || !out) return -1;
+    std::lock_guard<std::mutex> lk(q->mu);
+    static_assert(sizeof(bwamem_qc_counts_t) == (2 * QC_F_N + QC_S_N + 2 * QC_ORIENTATIONS) * 8, "bwamem_qc_counts_t is the counter words in order");
+    memcpy(out, &q->w[QC_W_FLAG], sizeof *out);                         // QC_W_FLAG .. QC_W_ISIZE_MAX are laid out as the struct is
+    return 0;
+}
+
+int64_t bwamem_hip_qc_array(const bwamem_qc_t* q, int which, uint64_t* dst, size_t cap)
+{
+    if (!q) return -1;
+    std::lock_guard<std::mutex> lk(q->mu);
+    size_t first = 0, n = 0, step = 1;
+    switch (which) {
+    case BWAMEM_HIP_QC_MAPQ: first = QC_W_MAPQ; n = BAMQC_MAPQ_BINS; break;
+    case BWAMEM_HIP_QC_QUAL: first = QC_W_QUAL; n = BAMQC_QUAL_BINS; break;
+    case BWAMEM_HIP_QC_ISIZE_FR: case BWAMEM_HIP_QC_ISIZE_RF: case BWAMEM_HIP_QC_ISIZE_TANDEM:
+        first = QC_W_ISIZE + (size_t)(which - BWAMEM_HIP_QC_ISIZE_FR) * BAMQC_ISIZE_BINS; n = BAMQC_ISIZE_BINS; break;
+    case BWAMEM_HIP_QC_CONTIG_MAPPED: first = QC_W_CONTIG; n = (size_t)q->n_contigs; step = 2; break;
+    case BWAMEM_HIP_QC_CONTIG_UNMAPPED: first = QC_W_CONTIG + 1; n = (size_t)q->n_contigs; step = 2; break;
+    default: return -1;
+    }
+    if (dst) for (size_t i = 0; i < n && i < cap; ++i) dst[i] = q->w[first + i * step];
+    return (int64_t)n;
+}
+
+void* bwamem_hip_qc_serialize(const bwamem_qc_t* q, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    if (!q) return nullptr;
+    std::lock_guard<std::mutex> lk(q->mu);
+    const size_t n = q->w.size();
+    uint64_t* p = (uint64_t*)malloc((QC_BLOB_HEAD + n) * 8);
+    if (!p) return nullptr;
+    p[0] = QC_BLOB_MAGIC; p[1] = QC_BLOB_VERSION; p[2] = (uint64_t)q->n_contigs; p[3] = (uint64_t)n;
+    memcpy(p + QC_BLOB_HEAD, q->w.data(), n * 8);
+    if (pBytes) *pBytes = (QC_BLOB_HEAD + n) * 8;
+    return p;
+}
+
+int bwamem_hip_qc_add_serialized(bwamem_qc_t* q, const void* blob, size_t n)
+{
+    return guarded("bwamem_hip_qc_add_serialized", -1, [&]() -> int {
+        if (!q || !blob || n < QC_BLOB_HEAD * 8) return -1;
+        uint64_t hd[QC_BLOB_HEAD];
+        memcpy(hd, blob, sizeof hd);
+        if (hd[0] != QC_BLOB_MAGIC || hd[1] != QC_BLOB_VERSION) { fprintf(stderr, "[bwamem_hip] qc_add_serialized: not a QC blob of version %d\n", (int)QC_BLOB_VERSION); return -1; }
+        if (hd[2] != (uint64_t)q->n_contigs || hd[3] != (uint64_t)q->w.size() || n != (QC_BLOB_HEAD + q->w.size()) * 8) {
+            fprintf(stderr, "[bwamem_hip] qc_add_serialized: the blob is of an index with %llu contigs, this QC object of one with %d\n", (unsigned long long)hd[2], q->n_contigs);
+            return -1;
+        }
+        std::vector<uint64_t> wds(q->w.size());
+        memcpy(wds.data(), (const uint8_t*)blob + QC_BLOB_HEAD * 8, wds.size() * 8);
+        qc_add_words(q, wds.data(), false);
+        return 0;
     });
 }
 

@@ -37,6 +37,7 @@
 #include <thread>
 #include <vector>
 #include "bam_encode.h"
+#include "bam_qc.h"
 #include "index_io.h"
 #include "../../include/bwamem_hip.h"
 
@@ -195,6 +196,12 @@ struct BatchOwner { bwamem_batch_t* b; ~BatchOwner() { bwamem_hip_batch_free(b);
 
 // the contig names and lengths of an open index (pipeline.cpp)
 const std::vector<ContigInfo>& bwamem_index_contigs(const bwaidx_t* idx);
+// the QC accumulator's two-step add and its contig table (pipeline.cpp)
+extern "C" {
+int bwamem_qc_batch_block(bwamem_qc_t* q, bwamem_batch_t* b, uint64_t** blk);
+void bwamem_qc_commit(bwamem_qc_t* q, const uint64_t* blk);
+const char* bwamem_qc_contig(const bwamem_qc_t* q, int i, int64_t* len);
+}
 
 // A plain gzip stream (one or several concatenated members, as `gzip` writes them) inflated on the host through libz.so.1: such a
 // stream has no member sizes and cannot be cut for the device (bgzf_inflate.h).  false with a message when the library is not
@@ -650,11 +657,14 @@ namespace {
 // totals, or null), sort if asked, compress, index if asked (fd_bai >= 0), write.  The header carries rg_line when there is one.
 // Everything is made before the first byte is written.
 int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off, const char* rg_line, int mark_dup,
-                      bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, unsigned tags = 0)
+                      bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, unsigned tags = 0, bwamem_qc_t* qc = nullptr)
 {
     if (tags && bwamem_hip_batch_set_tags(b, tags) != 0) return -1;
     if (bwamem_hip_batch_encode_bam(b, paired, names, name_off) != 0) return -1;
     if (mark_dup && bwamem_hip_batch_mark_duplicates(b, paired, counts) != 0) return -1;
+    uint64_t* qc_words_ = nullptr;                                      // the batch's QC block: reduced here, added when everything is written
+    if (qc && bwamem_qc_batch_block(qc, b, &qc_words_) != 0) return -1;
+    Freed qc_blk(qc_words_);
     if (sort && bwamem_hip_batch_sort_bam(b) != 0) return -1;
     size_t nh = 0, nzh = 0, nz = 0, nb = 0;
     Freed zh, z, bai;
@@ -677,6 +687,7 @@ int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* 
     if (write_header && !write_all(fd, (const uint8_t*)zh.p, nzh)) return -1;
     if (z.p ? !write_all(fd, (const uint8_t*)z.p, nz) : !write_all(fd, BGZF_EOF, sizeof BGZF_EOF)) return -1;      // no record: the EOF block alone
     if (fd_bai >= 0 && !write_all(fd_bai, (const uint8_t*)bai.p, nb)) return -1;
+    if (qc) bwamem_qc_commit(qc, (const uint64_t*)qc_blk.p);
     return 0;
 }
 
@@ -705,7 +716,8 @@ int request_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, c
 }
 
 int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
-                      const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, bool gz = false, unsigned tags = 0)
+                      const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, bool gz = false, unsigned tags = 0,
+                      bwamem_qc_t* qc = nullptr)
 {
     try {
         if (!idx || !opt || fd < 0) return -1;
@@ -718,7 +730,7 @@ int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, con
         if (!bo.b) return -1;
         if (rg_line && bwamem_hip_batch_set_read_group(bo.b, rg_line) != 0) return -1;
         if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
-        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, mark_dup, counts, sort, fd, fd_bai, write_header, tags);
+        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, mark_dup, counts, sort, fd, fd_bai, write_header, tags, qc);
     } catch (...) { return -1; }
 }
 
@@ -772,6 +784,13 @@ int bwamem_hip_align_fastq_gz_to_marked_bam(bwaidx_t* idx, const mem_opt_t* opt,
 int bwamem_hip_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
                             const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts)
 {
+    return bwamem_hip_fastq_to_bam_qc(idx, opt, pes, in1, n1, in2, n2, o, fd, fd_bai, counts, nullptr);
+}
+
+// ... with the batch added to a QC accumulator (bam_qc.h) after the marking and before the sort, once the whole call has succeeded
+int bwamem_hip_fastq_to_bam_qc(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
+                               const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts, bwamem_qc_t* qc)
+{
     if (counts) memset(counts, 0, sizeof *counts);
     bwamem_bam_options_t v;
     memset(&v, 0, sizeof v);
@@ -784,7 +803,93 @@ int bwamem_hip_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pesta
     const bool gz = is_gz(in1, n1);
     if (in2 && n2 && is_gz(in2, n2) != gz) { fprintf(stderr, "[bwamem_hip] fastq_to_bam: one input is compressed and the other is not\n"); return -1; }
     return fastq_to_bam_file("fastq_to_bam", idx, opt, pes, (const char*)in1, n1, (const char*)in2, n2, v.rg_line, v.mark_dup != 0, v.mark_dup ? counts : nullptr,
-                             v.sort != 0, fd, fd_bai, v.write_header, gz, v.tags);
+                             v.sort != 0, fd, fd_bai, v.write_header, gz, v.tags, qc);
+}
+
+// ---- the QC reports (bam_qc.h): plain text, '\n' line ends
+//   FLAGSTAT     sixteen lines "<passed> + <failed> <label>"; mapped, primary mapped, properly paired and singletons end in
+//                " (P : F)", the two columns as %.2f%% of total, primary, paired and paired, or N/A over a zero
+//   IDXSTATS     name, length, mapped, unmapped per contig in index order, then "*\t0\t0\t<unplaced>"
+//   SUMMARY      "key\tvalue": the single counters by their field names, then error_rate (mismatches / bases_mapped_cigar),
+//                average_length, average_quality, q20_bases, q30_bases, percent_duplication (primary_duplicates / primary_mapped,
+//                both columns); doubles as %.6f, N/A over a zero
+//   INSERT_SIZE  a header, a line per non-empty orientation (median and MAD %.1f, mean and standard deviation %.6f), an empty line,
+//                "insert_size\tFR\tRF\tTANDEM" and a line per bin that is non-zero in any orientation
+char* bwamem_hip_qc_report(const bwamem_qc_t* q, int kind, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    try {
+        bwamem_qc_counts_t c;
+        if (!q || bwamem_hip_qc_counts(q, &c) != 0) return nullptr;
+        std::string o;
+        char buf[512];
+        auto ratio = [&](uint64_t a, uint64_t b, const char* fmt, double scale) -> std::string {
+            if (!b) return "N/A";
+            char t[64]; snprintf(t, sizeof t, fmt, scale * (double)a / (double)b); return t;
+        };
+        auto array = [&](int which) { std::vector<uint64_t> a((size_t)std::max<int64_t>(bwamem_hip_qc_array(q, which, nullptr, 0), 0)); bwamem_hip_qc_array(q, which, a.data(), a.size()); return a; };
+        if (kind == BWAMEM_HIP_QC_FLAGSTAT) {
+            static const char* const label[16] = { "in total (QC-passed reads + QC-failed reads)", "primary", "secondary", "supplementary", "duplicates", "primary duplicates",
+                "mapped", "primary mapped", "paired in sequencing", "read1", "read2", "properly paired", "with itself and mate mapped", "singletons",
+                "with mate mapped to a different chr", "with mate mapped to a different chr (mapQ>=5)" };
+            const uint64_t (*row)[2] = &c.total;                        // the sixteen pairs are laid out in the order of the lines
+            for (int k = 0; k < 16; ++k) {
+                snprintf(buf, sizeof buf, "%llu + %llu %s", (unsigned long long)row[k][0], (unsigned long long)row[k][1], label[k]);
+                o += buf;
+                const uint64_t* den = k == 6 ? c.total : k == 7 ? c.primary : k == 11 || k == 13 ? c.paired : nullptr;
+                if (den) o += " (" + ratio(row[k][0], den[0], "%.2f%%", 100.0) + " : " + ratio(row[k][1], den[1], "%.2f%%", 100.0) + ")";
+                o += "\n";
+            }
+        } else if (kind == BWAMEM_HIP_QC_IDXSTATS) {
+            const std::vector<uint64_t> m = array(BWAMEM_HIP_QC_CONTIG_MAPPED), u = array(BWAMEM_HIP_QC_CONTIG_UNMAPPED);
+            for (size_t i = 0; i < m.size(); ++i) {
+                int64_t len = 0;
+                const char* name = bwamem_qc_contig(q, (int)i, &len);
+                o += name ? name : "";
+                snprintf(buf, sizeof buf, "\t%lld\t%llu\t%llu\n", (long long)len, (unsigned long long)m[i], (unsigned long long)u[i]);
+                o += buf;
+            }
+            snprintf(buf, sizeof buf, "*\t0\t0\t%llu\n", (unsigned long long)c.unplaced);
+            o += buf;
+        } else if (kind == BWAMEM_HIP_QC_SUMMARY) {
+            static const char* const key[14] = { "unplaced", "sequences", "total_length", "max_length", "reads_mq0", "bases_mapped", "bases_mapped_cigar", "bases_soft_clipped",
+                "ins_events", "ins_bases", "del_events", "del_bases", "mismatches", "records_without_nm" };
+            const uint64_t* val = &c.unplaced;
+            for (int k = 0; k < 14; ++k) { snprintf(buf, sizeof buf, "%s\t%llu\n", key[k], (unsigned long long)val[k]); o += buf; }
+            const std::vector<uint64_t> qh = array(BWAMEM_HIP_QC_QUAL);
+            uint64_t nq = 0, sq = 0, q20 = 0, q30 = 0;
+            for (size_t v = 0; v < qh.size(); ++v) { nq += qh[v]; sq += qh[v] * v; if (v >= 20) q20 += qh[v]; if (v >= 30) q30 += qh[v]; }
+            o += "error_rate\t" + ratio(c.mismatches, c.bases_mapped_cigar, "%.6f", 1.0) + "\n";
+            o += "average_length\t" + ratio(c.total_length, c.sequences, "%.6f", 1.0) + "\n";
+            o += "average_quality\t" + ratio(sq, nq, "%.6f", 1.0) + "\n";
+            snprintf(buf, sizeof buf, "q20_bases\t%llu\nq30_bases\t%llu\n", (unsigned long long)q20, (unsigned long long)q30);
+            o += buf;
+            o += "percent_duplication\t" + ratio(c.primary_duplicates[0] + c.primary_duplicates[1], c.primary_mapped[0] + c.primary_mapped[1], "%.6f", 1.0) + "\n";
+        } else if (kind == BWAMEM_HIP_QC_INSERT_SIZE) {
+            static const char* const name[3] = { "FR", "RF", "TANDEM" };
+            std::vector<uint64_t> h[3];
+            o += "PAIR_ORIENTATION\tREAD_PAIRS\tMIN_INSERT_SIZE\tMAX_INSERT_SIZE\tMEDIAN_INSERT_SIZE\tMEDIAN_ABSOLUTE_DEVIATION\tMEAN_INSERT_SIZE\tSTANDARD_DEVIATION\n";
+            for (int k = 0; k < 3; ++k) {
+                h[k] = array(BWAMEM_HIP_QC_ISIZE_FR + k);
+                const QcIsizeStats s = qc_isize_stats(h[k].data());
+                if (!s.n) continue;
+                snprintf(buf, sizeof buf, "%s\t%llu\t%llu\t%llu\t%.1f\t%.1f\t%.6f\t%.6f\n", name[k], (unsigned long long)s.n, (unsigned long long)c.isize_min[k],
+                         (unsigned long long)c.isize_max[k], s.median, s.mad, s.mean, s.sd);
+                o += buf;
+            }
+            o += "\ninsert_size\tFR\tRF\tTANDEM\n";
+            for (int v = 0; v < BAMQC_ISIZE_BINS; ++v)
+                if (h[0][v] | h[1][v] | h[2][v]) {
+                    snprintf(buf, sizeof buf, "%d\t%llu\t%llu\t%llu\n", v, (unsigned long long)h[0][v], (unsigned long long)h[1][v], (unsigned long long)h[2][v]);
+                    o += buf;
+                }
+        } else return nullptr;
+        char* r = (char*)malloc(o.size() + 1);
+        if (!r) return nullptr;
+        memcpy(r, o.c_str(), o.size() + 1);
+        if (pBytes) *pBytes = o.size();
+        return r;
+    } catch (...) { return nullptr; }
 }
 
 }  // extern "C"

@@ -97,3 +97,21 @@ def align_shard(dll, idx, opts, reads, rank, world, paired=False, pes=None, dist
         return out.raw[:n]
     finally:
         dll.bwamem_hip_batch_free(batch)
+
+
+def gather_qc(dist, qc, dst=0):
+    """Whole-sample QC over the ranks (csrc/bam_qc.h): every rank's accumulator (a bwamem.BwaMemQc) is serialized and gathered, and
+    rank `dst` adds the others' to its own -- the counters are sums, so nothing else is exchanged.  Returns qc on rank dst, None
+    elsewhere.  Every rank's index has the same contigs, so the blobs are of one size."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    mine = torch.frombuffer(bytearray(qc.serialize()), dtype=torch.uint8).to(dev)
+    world, rank = dist.get_world_size(), dist.get_rank()
+    blobs = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(blobs, mine)
+    if rank != dst:
+        return None
+    for r in range(world):
+        if r != rank:
+            qc.add(blobs[r].cpu().numpy().tobytes())
+    return qc

@@ -303,6 +303,52 @@ char*  bwamem_hip_response_to_sam_tags(bwaidx_t* idx, const char* pSeq, const vo
 int    bwamem_hip_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
                                const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts);
 
+/* Alignment QC on the device (csrc/bam_qc.h; additive: without a QC object every entry point above writes byte for byte what it
+ * did).  flagstat, idxstats, the summary numbers of `samtools stats` and the insert-size metrics of Picard, as a reduction over the
+ * BAM records of a batch while they are in HBM.  The rule is at the top of csrc/bam_qc.h and is defined on the records alone; parity
+ * with the output of samtools or Picard is not checked anywhere.  A bwamem_qc_t is an accumulator in host memory: it adds up any
+ * number of calls, batches on any replica of the handle, and the serialized accumulators of other devices, ranks or runs.  A call
+ * that fails leaves it exactly as it was.
+ *   _qc_create      an empty accumulator for the contigs (names, lengths) of idx; idx must outlive it for _qc_add_records_device.
+ *   _qc_add_batch   after _encode_bam; after _mark_duplicates to see 0x400; before or after _sort_bam (the result is the same).
+ *                   Non-zero with a message without encoded records, for a batch of an index with another contig count, or when a
+ *                   record does not parse.  0 and nothing added for a batch without records.
+ *   _qc_add_records_device   tooling: host bytes, any stream of BAM records (block_size and body, no header), uploaded and reduced
+ *                   by the same kernels on the device of the accumulator's index.
+ *   _qc_counts      the counters; _qc_array: one array (BWAMEM_HIP_QC_*) into dst[0, cap), returns its length (dst may be NULL),
+ *                   -1 for an unknown array.
+ *   _qc_serialize   the accumulator as bytes (jnibwa_free): four 64-bit words -- a magic, the version, n_contigs, the word count --
+ *                   and the words.  _qc_add_serialized adds such a blob; it refuses another version or n_contigs, and then changes
+ *                   nothing.
+ *   _qc_report      plain text, '\n' line ends, NUL-terminated (jnibwa_free); *pBytes without the NUL.  _FLAGSTAT: the sixteen lines of
+ *                   samtools flagstat; _IDXSTATS: name, length, mapped, unmapped per contig and the '*' line; _SUMMARY: key<TAB>value
+ *                   for every single counter and the derived numbers; _INSERT_SIZE: the metrics per orientation and the histogram.
+ *                   The formats are in csrc/sam_writer.cpp.
+ *   bwamem_hip_fastq_to_bam_qc   bwamem_hip_fastq_to_bam with the batch added to qc after mark-duplicates (when asked for) and
+ *                   before the sort -- only if the whole call returns 0.  qc == NULL: bwamem_hip_fastq_to_bam. */
+typedef struct bwamem_qc_s bwamem_qc_t;
+typedef struct {
+    uint64_t total[2], primary[2], secondary[2], supplementary[2], duplicates[2], primary_duplicates[2], mapped[2], primary_mapped[2], paired[2], read1[2], read2[2],
+             properly_paired[2], both_mapped[2], singletons[2], mate_diff_chr[2], mate_diff_chr_mapq5[2];       /* [0] QC-passed, [1] QC-failed (0x200) */
+    uint64_t unplaced, sequences, total_length, max_length, reads_mq0, bases_mapped, bases_mapped_cigar, bases_soft_clipped, ins_events, ins_bases, del_events,
+             del_bases, mismatches, records_without_nm;
+    uint64_t isize_min[3], isize_max[3];        /* FR, RF, TANDEM; UINT32_MAX and 0 when empty */
+} bwamem_qc_counts_t;
+enum { BWAMEM_HIP_QC_MAPQ = 0, BWAMEM_HIP_QC_QUAL, BWAMEM_HIP_QC_ISIZE_FR, BWAMEM_HIP_QC_ISIZE_RF, BWAMEM_HIP_QC_ISIZE_TANDEM, BWAMEM_HIP_QC_CONTIG_MAPPED,
+       BWAMEM_HIP_QC_CONTIG_UNMAPPED };
+enum { BWAMEM_HIP_QC_FLAGSTAT = 0, BWAMEM_HIP_QC_IDXSTATS, BWAMEM_HIP_QC_SUMMARY, BWAMEM_HIP_QC_INSERT_SIZE };
+bwamem_qc_t* bwamem_hip_qc_create(bwaidx_t* idx);
+void   bwamem_hip_qc_free(bwamem_qc_t* q);
+int    bwamem_hip_qc_add_batch(bwamem_qc_t* q, bwamem_batch_t* b);
+int    bwamem_hip_qc_add_records_device(bwamem_qc_t* q, const void* records, size_t nBytes);
+int    bwamem_hip_qc_counts(const bwamem_qc_t* q, bwamem_qc_counts_t* out);
+int64_t bwamem_hip_qc_array(const bwamem_qc_t* q, int which, uint64_t* dst, size_t cap);
+void*  bwamem_hip_qc_serialize(const bwamem_qc_t* q, size_t* pBytes);                      /* jnibwa_free */
+int    bwamem_hip_qc_add_serialized(bwamem_qc_t* q, const void* blob, size_t n);
+char*  bwamem_hip_qc_report(const bwamem_qc_t* q, int kind, size_t* pBytes);               /* jnibwa_free */
+int    bwamem_hip_fastq_to_bam_qc(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
+                                  const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts, bwamem_qc_t* qc);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
