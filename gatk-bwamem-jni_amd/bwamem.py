@@ -121,6 +121,30 @@ _lib.bwamem_hip_qc_report.restype = _vp; _lib.bwamem_hip_qc_report.argtypes = [_
 _lib.bwamem_hip_fastq_to_bam_qc.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.POINTER(_BamOptions), ctypes.c_int, ctypes.c_int,
                                             ctypes.POINTER(_DupCounts), _vp]
 
+# base-level QC (csrc/bam_baseqc.h): the tables in the order of BWAMEM_HIP_BASEQC_*
+_BASEQC_ARRAYS = {"base": 0, "qual_sum": 1, "qual_n": 2, "aligned": 3, "mism": 4, "ins": 5, "del_ev": 6, "soft": 7, "read_gc": 8, "gcb_reads": 9, "gcb_qual_sum": 10,
+                  "gcb_qual_n": 11}
+_BASEQC_REPORTS = {"cycles": 0, "gc": 1}
+
+
+class _BaseQcCounts(ctypes.Structure):
+    """bwamem_baseqc_counts_t"""
+    _fields_ = [("records", ctypes.c_uint64 * 3), ("qcfail_skipped", ctypes.c_uint64), ("gcb_skipped", ctypes.c_uint64)]
+
+
+_lib.bwamem_hip_baseqc_create.restype = _vp; _lib.bwamem_hip_baseqc_create.argtypes = [_vp]
+_lib.bwamem_hip_baseqc_free.restype = None; _lib.bwamem_hip_baseqc_free.argtypes = [_vp]
+_lib.bwamem_hip_baseqc_add_batch.argtypes = [_vp, _vp]
+_lib.bwamem_hip_baseqc_add_records_device.argtypes = [_vp, ctypes.c_char_p, _sz]
+_lib.bwamem_hip_baseqc_counts.argtypes = [_vp, ctypes.POINTER(_BaseQcCounts)]
+_lib.bwamem_hip_baseqc_array.restype = _i64; _lib.bwamem_hip_baseqc_array.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64), _sz]
+_lib.bwamem_hip_baseqc_serialize.restype = _vp; _lib.bwamem_hip_baseqc_serialize.argtypes = [_vp, ctypes.POINTER(_sz)]
+_lib.bwamem_hip_baseqc_add_serialized.argtypes = [_vp, ctypes.c_char_p, _sz]
+_lib.bwamem_hip_baseqc_report.restype = _vp; _lib.bwamem_hip_baseqc_report.argtypes = [_vp, ctypes.c_int, ctypes.POINTER(_sz)]
+_lib.bwamem_hip_index_gc_windows.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint64)]
+_lib.bwamem_hip_fastq_to_bam_metrics.argtypes = [_vp, _vp, _vp, ctypes.c_char_p, _sz, ctypes.c_char_p, _sz, ctypes.POINTER(_BamOptions), ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(_DupCounts), _vp, _vp]
+
 
 def _tag_mask(tags):
     """("SA", "MC", "MQ") -> BWAMEM_HIP_TAG_* OR-ed"""
@@ -212,6 +236,77 @@ class BwaMemQc:
         blob = other.serialize() if isinstance(other, BwaMemQc) else bytes(other)
         if _lib.bwamem_hip_qc_add_serialized(self._ptr(), blob, len(blob)) != 0:
             raise ValueError("the QC blob was refused: another version, or an index with another number of contigs")
+
+
+class BwaMemBaseQc:
+    """Additive: a base-level QC accumulator (csrc/bam_baseqc.h) -- quality, base composition, mismatches, indels and soft clips per
+    sequencing cycle and end, the reads' GC histograms and GC bias over 100-base reference windows -- of the records of any number of
+    alignSeqsToBam / alignFastqToBam calls (base_qc=...), reduced on the device against the resident reference.  The index must stay
+    open while batches are added.  serialize() / add() have the shape of BwaMemQc's, so sharding.gather_qc carries this accumulator
+    unchanged."""
+
+    def __init__(self, index):
+        self.index = index
+        self._q = _lib.bwamem_hip_baseqc_create(index.refIndex())
+        index.deRefIndex()
+        if not self._q:
+            raise RuntimeError("Unable to create a base-QC accumulator for bwa-mem index %s" % index.indexImageFile)
+
+    def _ptr(self):
+        if not self._q:
+            raise RuntimeError("The base-QC accumulator has been closed.")
+        return self._q
+
+    def close(self):
+        if self._q:
+            _lib.bwamem_hip_baseqc_free(self._q)
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def counts(self):
+        """records (one count per end: unpaired, first, second), qcfail_skipped, gcb_skipped"""
+        c = _BaseQcCounts()
+        if _lib.bwamem_hip_baseqc_counts(self._ptr(), ctypes.byref(c)) != 0:
+            raise RuntimeError("bwamem_hip_baseqc_counts failed")
+        return dict(records=[int(x) for x in c.records], qcfail_skipped=int(c.qcfail_skipped), gcb_skipped=int(c.gcb_skipped))
+
+    def array(self, name):
+        """one table as a flat list of ints.  qual_sum, qual_n, aligned, mism, ins, del_ev, soft: [end][cycle], 3 x 1024; base:
+        [end][cycle][A C G T N]; read_gc: [end][101]; gcb_reads, gcb_qual_sum, gcb_qual_n: [101]"""
+        if name not in _BASEQC_ARRAYS:
+            raise ValueError("unknown base-QC table %r: %s" % (name, ", ".join(sorted(_BASEQC_ARRAYS))))
+        n = _lib.bwamem_hip_baseqc_array(self._ptr(), _BASEQC_ARRAYS[name], None, 0)
+        buf = (ctypes.c_uint64 * max(n, 1))()
+        _lib.bwamem_hip_baseqc_array(self._ptr(), _BASEQC_ARRAYS[name], buf, n)
+        return [int(x) for x in buf[:n]]
+
+    def _report(self, kind):
+        sz = ctypes.c_size_t()
+        p = _lib.bwamem_hip_baseqc_report(self._ptr(), _BASEQC_REPORTS[kind], ctypes.byref(sz))
+        if not p:
+            raise RuntimeError("bwamem_hip_baseqc_report failed")
+        return _taken(p, sz.value).decode()
+
+    def cycles(self): return self._report("cycles")
+    def gcBias(self): return self._report("gc")
+
+    def serialize(self):
+        sz = ctypes.c_size_t()
+        p = _lib.bwamem_hip_baseqc_serialize(self._ptr(), ctypes.byref(sz))
+        if not p:
+            raise RuntimeError("bwamem_hip_baseqc_serialize failed")
+        return _taken(p, sz.value)
+
+    def add(self, other):
+        """adds another accumulator, or the bytes of one (serialize(): other calls, devices, ranks); ValueError when it is refused"""
+        blob = other.serialize() if isinstance(other, BwaMemBaseQc) else bytes(other)
+        if _lib.bwamem_hip_baseqc_add_serialized(self._ptr(), blob, len(blob)) != 0:
+            raise ValueError("the base-QC blob was refused: another type or version, or an index with another number of contigs")
 
 
 class CouldNotReadImageException(RuntimeError):
@@ -380,6 +475,18 @@ class BwaMemIndex:
     def getReferenceContigNames(self):
         return self.refContigNames
 
+    def gcWindows(self):
+        """Additive: windows[g], g = 0..100 -- the number of 100-base windows of the reference that touch no .amb hole and hold g C/G
+        bases: the denominator of GC bias (csrc/bam_baseqc.h), computed on the device once per index"""
+        out = (ctypes.c_uint64 * 101)()
+        idx = self.refIndex()
+        try:
+            if _lib.bwamem_hip_index_gc_windows(idx, out) != 0:
+                raise RuntimeError("bwamem_hip_index_gc_windows failed for bwa-mem index %s" % self.indexImageFile)
+        finally:
+            self.deRefIndex()
+        return [int(x) for x in out]
+
     @staticmethod
     def getBWAVersion():
         return _lib.jnibwa_getVersion().decode()
@@ -485,6 +592,11 @@ class BwaMemAligner:
         """Additive: an empty QC accumulator (BwaMemQc) for this aligner's index, to be handed to alignSeqsToBam / alignFastqToBam"""
         return BwaMemQc(self.index)
 
+    def newBaseQc(self):
+        """Additive: an empty base-level QC accumulator (BwaMemBaseQc) for this aligner's index, to be handed to alignSeqsToBam /
+        alignFastqToBam as base_qc="""
+        return BwaMemBaseQc(self.index)
+
     def alignSeqsRaw(self, sequences, func=lambda s: s):
         """the raw native response (BwaMemAligner.java:192-214)"""
         opts = self._getOpts()
@@ -500,7 +612,7 @@ class BwaMemAligner:
             self.index.deRefIndex()
 
     def alignSeqsToBam(self, sequences, path, names=None, level=1, func=lambda s: s, device=False, sort=False, index_path=None, quals=None,
-                       read_group=None, mark_duplicates=False, tags=(), qc=None):
+                       read_group=None, mark_duplicates=False, tags=(), qc=None, base_qc=None):
         """Additive (no Java counterpart): align and write a BAM file -- header, the records encoded on the device, BGZF framing at
         `level` (0 = stored blocks; 1..9 need libz.so.1), EOF block.  names: one per sequence (1..254 bytes each), else
         "r<index>" / "p<pair index>".  The insert-size statistics are the aligner's (setProperPairEndStats / inferred).
@@ -514,19 +626,20 @@ class BwaMemAligner:
         are marked on the device within this call before the sort (csrc/bam_dup.h), and the counts are returned as a dict.
         tags: any of "SA", "MC", "MQ": the records carry them, built on the device (csrc/bam_encode.h); implies device=True.
         qc: a BwaMemQc (newQc()): the records of this call are added to it on the device, after the marking and before the sort, once
-        the call has succeeded (csrc/bam_qc.h); accepted where mark_duplicates is."""
+        the call has succeeded (csrc/bam_qc.h); accepted where mark_duplicates is.
+        base_qc: a BwaMemBaseQc (newBaseQc()): the same for the base-level tables (csrc/bam_baseqc.h)."""
         mask = _tag_mask(tags)
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
-        if (mark_duplicates or qc is not None) and not (device or sort or quals is not None or read_group is not None or mask):
-            raise ValueError("mark_duplicates and qc need device=True or sort=True: the host-framing path takes the records off the device unmarked")
+        if (mark_duplicates or qc is not None or base_qc is not None) and not (device or sort or quals is not None or read_group is not None or mask):
+            raise ValueError("mark_duplicates, qc and base_qc need device=True or sort=True: the host-framing path takes the records off the device unmarked")
         opts = self._getOpts()
         seqs = [func(e) for e in sequences]
         seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
         if names is not None and len(names) != len(seqs):
             raise ValueError("%d names for %d sequences" % (len(names), len(seqs)))
-        if quals is not None or read_group is not None or mask or qc is not None:
-            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group, mark_duplicates, mask, qc)
+        if quals is not None or read_group is not None or mask or qc is not None or base_qc is not None:
+            return self._alignSeqsToBamBatch(seqs, path, names, sort, index_path, quals, read_group, mark_duplicates, mask, qc, base_qc)
         buf = struct.pack("=i", len(seqs)) + b"".join(s + b"\0" for s in seqs)
         arr = None
         if names is not None:
@@ -565,7 +678,7 @@ class BwaMemAligner:
             raise RuntimeError("Unable to write alignments of bwa-mem index %s to %s" % (self.index.indexImageFile, path))
         return counts.as_dict() if mark_duplicates else None
 
-    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group, mark_duplicates=False, tag_mask=0, qc=None):
+    def _alignSeqsToBamBatch(self, seqs, path, names, sort, index_path, quals, read_group, mark_duplicates=False, tag_mask=0, qc=None, base_qc=None):
         """alignSeqsToBam through the batch calls, which take qualities and a read group; nothing is written unless all of it succeeds"""
         if quals is not None:
             quals = [q.encode() if isinstance(q, str) else bytes(q) for q in quals]
@@ -612,6 +725,13 @@ class BwaMemAligner:
                     raise fail
                 qc_blob = mine.serialize()
                 mine.close()
+            if base_qc is not None:
+                base_qc._ptr()
+                mine = BwaMemBaseQc(self.index)
+                if _lib.bwamem_hip_baseqc_add_batch(mine._ptr(), b) != 0:
+                    raise fail
+                base_blob = mine.serialize()
+                mine.close()
             if sort and _lib.bwamem_hip_batch_sort_bam(b) != 0:
                 raise fail
             sz = ctypes.c_size_t()
@@ -646,9 +766,11 @@ class BwaMemAligner:
                 f.write(bai)
         if qc is not None:
             qc.add(qc_blob)
+        if base_qc is not None:
+            base_qc.add(base_blob)
         return counts.as_dict() if mark_duplicates else None
 
-    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False, tags=(), qc=None):
+    def alignFastqToBam(self, fastq1, path, fastq2=None, read_group=None, sort=False, index_path=None, mark_duplicates=False, tags=(), qc=None, base_qc=None):
         """Additive: FASTQ in, a BAM file out.  fastq1 / fastq2: FASTQ text (bytes), or the path of a FASTQ file (str); bytes or a
         file that begin with 1f 8b are compressed FASTQ and are handed over as they are: BGZF (bgzip) is inflated on the device, plain
         gzip on the host (csrc/bgzf_inflate.h);
@@ -658,7 +780,8 @@ class BwaMemAligner:
         mark_duplicates=True: duplicates are marked on the device within this call, before the sort (csrc/bam_dup.h -- the highest
         sum of base qualities keeps a group's place), and the counts are returned as a dict.
         tags: any of "SA", "MC", "MQ", as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam.
-        qc: a BwaMemQc, as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam_qc."""
+        qc: a BwaMemQc, as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam_qc.
+        base_qc: a BwaMemBaseQc, as for alignSeqsToBam; the call then goes through bwamem_hip_fastq_to_bam_metrics."""
         mask = _tag_mask(tags)
         if index_path is not None and not sort:
             raise ValueError("index_path needs sort=True: only a coordinate-sorted file has a BAI index")
@@ -679,7 +802,11 @@ class BwaMemAligner:
             fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
             fd_bai = os.open(index_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if index_path is not None else -1
             try:
-                if mask or qc is not None:
+                if base_qc is not None:
+                    o = _BamOptions(size=ctypes.sizeof(_BamOptions), rg_line=rg, sort=1 if sort else 0, mark_dup=1 if mark_duplicates else 0, tags=mask, write_header=1)
+                    rc = _lib.bwamem_hip_fastq_to_bam_metrics(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, ctypes.byref(o), fd, fd_bai,
+                                                              ctypes.byref(counts), qc._ptr() if qc is not None else None, base_qc._ptr())
+                elif mask or qc is not None:
                     o = _BamOptions(size=ctypes.sizeof(_BamOptions), rg_line=rg, sort=1 if sort else 0, mark_dup=1 if mark_duplicates else 0, tags=mask, write_header=1)
                     rc = _lib.bwamem_hip_fastq_to_bam_qc(idx, opts, pb, t1, len(t1), t2, len(t2) if t2 is not None else 0, ctypes.byref(o), fd, fd_bai, ctypes.byref(counts),
                                                          qc._ptr() if qc is not None else None)

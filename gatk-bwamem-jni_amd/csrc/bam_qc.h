@@ -7,7 +7,7 @@
 // (bwamem_qc_t) is a block of integers, and adding two blocks is adding their words (min / max for the six extremes).  The
 // definitions restate what samtools flagstat / idxstats / stats and Picard CollectInsertSizeMetrics document; parity with the
 // output of those tools is not checked anywhere in this project (its machines have none of them): the checked contract is the rule
-// below.  Per-base depth, per-cycle metrics and GC bias are not built.
+// below.  Per-cycle metrics and GC bias are a reduction of their own (bam_baseqc.h); per-base depth is not built.
 //
 // A record is block_size (int32) and block_size bytes of body; the fields sit where dup_end() (bam_dup.h) reads them: refID at 4,
 // pos 8, l_read_name 12, mapq 13, n_cigar 16, flag 18, l_seq 20, next_refID 24, next_pos 28, tlen 32, then the name, the CIGAR,

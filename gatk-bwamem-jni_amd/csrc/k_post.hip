@@ -1557,6 +1557,350 @@ __global__ void __launch_bounds__(QC_THREADS) k_qc_qual(QcView v)
     }
 }
 
+// ------------------------------------------------------------------ base-level QC: tables per sequencing cycle and GC bias (bam_baseqc.h)
+#define BQC_THREADS 256
+// A workgroup's 32-bit copy of a 64-bit word of the block.  For the batches of this library a copy cannot wrap: a workgroup adds at
+// most 255 (one QUAL byte) per record to a word, and a call holds fewer than 2^31 / 36 records of 36 bytes or more in under 2 GiB.
+// bwamem_hip_baseqc_add_records_device takes streams up to 2^40 bytes, for which no such bound holds, so a wrap is carried into the
+// word itself: the flush then adds what is left, and the sum is exact for any stream.
+static __device__ inline void bqc_lds_add(uint32_t* s, uint32_t x, unsigned long long* word)
+{
+    const uint32_t old = atomicAdd(s, x);
+    if (old + x < old) atomicAdd(word, 1ull << 32);
+}
+// ... for a sum that may itself exceed 32 bits: the high part goes to the word directly
+static __device__ inline void bqc_lds_add64(uint32_t* s, unsigned long long x, unsigned long long* word)
+{
+    bqc_lds_add(s, (uint32_t)x, word);
+    if (x >> 32) atomicAdd(word, x >> 32 << 32);
+}
+// one count of a table: the workgroup's copy below BASEQC_LDS_CYCLES, the lane's register for the capped last bin, else HBM
+template <typename C>
+static __device__ inline void bqc_count(uint32_t* s_tab, unsigned long long* g_tab, int32_t e, int32_t bin, uint32_t x, C& cap)
+{
+    if (bin < BASEQC_LDS_CYCLES) bqc_lds_add(&s_tab[e * BASEQC_LDS_CYCLES + bin], x, &g_tab[e * BASEQC_CYCLES + bin]);
+    else if (bin == BASEQC_CYCLES - 1) cap += x;
+    else atomicAdd(&g_tab[e * BASEQC_CYCLES + bin], (unsigned long long)x);
+}
+static __device__ inline void bqc_flush(const uint32_t* s_tab, unsigned long long* g_tab, int tid)
+{
+    for (int j = tid; j < BASEQC_ENDS * BASEQC_LDS_CYCLES; j += BQC_THREADS)
+        if (s_tab[j]) atomicAdd(&g_tab[(j / BASEQC_LDS_CYCLES) * BASEQC_CYCLES + j % BASEQC_LDS_CYCLES], (unsigned long long)s_tab[j]);
+}
+
+// (a) every check of bam_baseqc.h, one lane per item (a read's records, or one record): the errors, records[], qcfail_skipped and the
+// longest contributing read.  Reads no reference byte; the other kernels run only when it leaves no error.
+__global__ void __launch_bounds__(BQC_THREADS) k_bqc_check(BqcView v)
+{
+    __shared__ unsigned long long s_cnt[BASEQC_ENDS + 1];
+    __shared__ int32_t s_ext[2];                                       // the longest read, the errors
+    const int tid = (int)threadIdx.x, lane = tid & 63;
+    if (tid < BASEQC_ENDS + 1) s_cnt[tid] = 0;
+    if (tid < 2) s_ext[tid] = 0;
+    __syncthreads();
+    unsigned long long n[BASEQC_ENDS + 1] = { 0, 0, 0, 0 };
+    int32_t max_len = 0, err = 0;
+    for (int64_t i = (int64_t)blockIdx.x * BQC_THREADS + tid; i < v.n_items; i += (int64_t)gridDim.x * BQC_THREADS) {
+        int64_t o = v.off[i];
+        const int64_t hi = v.off[i + 1];
+        while (o < hi) {
+            int e = 0;
+            int64_t size = 0;
+            BqcRec r = {};
+            if (hi - o < BAMSORT_MIN_REC) e = BASEQC_ERR_WALK;
+            else {
+                size = 4 + (int64_t)(int32_t)bamsort_ld32(v.bam + o);
+                if (size < BAMSORT_MIN_REC || size > hi - o || (!v.grouped && size != hi - o)) e = BASEQC_ERR_WALK;
+            }
+            if (!e) e = bqc_fields(v.bam + o, size, v.n_contigs, r);
+            if (!e && r.primary && !(r.f & 4)) e = bqc_mapped(v.bam + o, v.ann_len, r);
+            if (e) { err |= e; break; }
+            if (r.counted) {
+                n[0] += r.e == 0; n[1] += r.e == 1; n[2] += r.e == 2;
+                if (r.l_seq > max_len) max_len = r.l_seq;
+            } else if (r.primary) n[BASEQC_ENDS] += 1;
+            o += size;
+        }
+    }
+    for (int k = 0; k < BASEQC_ENDS + 1; ++k) {
+        const unsigned long long t = qc_wave_sum(n[k]);
+        if (lane == 0 && t) atomicAdd(&s_cnt[k], t);
+    }
+    max_len = qc_wave_max(max_len);
+    for (int o = 32; o > 0; o >>= 1) err |= __shfl_xor(err, o);
+    if (lane == 0) {
+        if (max_len) atomicMax(&s_ext[0], max_len);
+        if (err) atomicOr(&s_ext[1], err);
+    }
+    __syncthreads();
+    if (tid < BASEQC_ENDS + 1 && s_cnt[tid]) atomicAdd(&v.blk[BQ_W_RECORDS + tid], s_cnt[tid]);       // (qcfail_skipped follows records[])
+    if (tid == 0 && s_ext[0]) atomicMax((int*)&v.blk[BQ_W_MAX_LEN], s_ext[0]);                        // (the low half of a little-endian word)
+    if (tid == 0 && s_ext[1]) atomicOr((int*)&v.blk[BQ_W_ERR], s_ext[1]);
+}
+
+// The next record among the item's bytes [o, hi) that counts (mapped: that is a mapped primary and passes bqc_mapped): its fields in
+// r, o behind it.  Every lane of a group takes the same steps.  Where the bytes do not chain the item ends (k_bqc_check has refused
+// such a stream): every bound is checked again here.
+static __device__ inline bool bqc_next(const BqcView& v, int64_t& o, int64_t hi, bool mapped, const uint8_t*& rec, BqcRec& r)
+{
+    while (hi - o >= BAMSORT_MIN_REC) {
+        rec = v.bam + o;
+        const int64_t size = 4 + (int64_t)(int32_t)bamsort_ld32(rec);
+        if (size < BAMSORT_MIN_REC || size > hi - o) break;
+        o += size;
+        if (bqc_fields(rec, size, v.n_contigs, r) != 0) break;
+        if (mapped ? r.mapped && bqc_mapped(rec, v.ann_len, r) == 0 : r.counted) return true;
+    }
+    o = hi;
+    return false;
+}
+
+// (b) base[], qual_sum[] / qual_n[] and read_gc[], by lane groups of G lanes per item as k_qc_qual has them.  The group shares out the
+// aligned 32-bit words of QUAL, the up to three bytes before the first and after the last going singly; a lane reads the SEQ bytes of
+// its own indices.  The group's rounds are uniform over the wave: the reads' GC is summed over the group by shuffles.
+template <int G>
+__global__ void __launch_bounds__(BQC_THREADS) k_bqc_bases(BqcView v)
+{
+    __shared__ uint32_t s_base[BASEQC_ENDS * BASEQC_LDS_CYCLES * BASEQC_BASES], s_qs[BASEQC_ENDS * BASEQC_LDS_CYCLES], s_qn[BASEQC_ENDS * BASEQC_LDS_CYCLES];
+    __shared__ uint32_t s_rgc[BASEQC_ENDS * BASEQC_GC_BINS];
+    const int tid = (int)threadIdx.x, sub = tid % G, per = BQC_THREADS / G;
+    for (int j = tid; j < BASEQC_ENDS * BASEQC_LDS_CYCLES * BASEQC_BASES; j += BQC_THREADS) s_base[j] = 0;
+    for (int j = tid; j < BASEQC_ENDS * BASEQC_LDS_CYCLES; j += BQC_THREADS) { s_qs[j] = 0; s_qn[j] = 0; }
+    for (int j = tid; j < BASEQC_ENDS * BASEQC_GC_BINS; j += BQC_THREADS) s_rgc[j] = 0;
+    __syncthreads();
+    unsigned long long* const g_base = v.blk + BQ_W_BASE;
+    for (int64_t first = (int64_t)blockIdx.x * per; first < v.n_items; first += (int64_t)gridDim.x * per) {
+        const int64_t i = first + tid / G;
+        int64_t o = 0, hi = 0;
+        if (i < v.n_items) { o = v.off[i]; hi = v.off[i + 1]; }
+        for (;;) {
+            BqcRec r = {};
+            const uint8_t* rec = nullptr;
+            const bool have = bqc_next(v, o, hi, false, rec, r);
+            if (!wave_any(have)) break;
+            uint32_t gc = 0, acgt = 0;
+            if (have && r.l_seq > 0) {
+                const uint8_t* seq = rec + r.seq_off;
+                const uint8_t* q = rec + r.qual_off;
+                const int32_t n = r.l_seq, e = r.e;
+                const bool hq = q[0] != 0xff;
+                uint32_t cap_b[BASEQC_BASES] = { 0, 0, 0, 0, 0 }, cap_qn = 0;
+                unsigned long long cap_qs = 0;                                    // (up to 255 per base of a record of any length)
+                auto put = [&](int64_t idx, uint32_t qv) {
+                    const int32_t code = bqc_code(seq, idx), k = bqc_column(code, r.rev), bin = bqc_bin(r, idx);
+                    if (code < 4) { ++acgt; gc += (code == 1 || code == 2) ? 1u : 0u; }
+                    if (bin < BASEQC_LDS_CYCLES) {
+                        const int32_t w = e * BASEQC_LDS_CYCLES + bin;
+                        bqc_lds_add(&s_base[w * BASEQC_BASES + k], 1u, &g_base[(e * BASEQC_CYCLES + bin) * BASEQC_BASES + k]);
+                    } else if (bin == BASEQC_CYCLES - 1) {
+#pragma unroll
+                        for (int kk = 0; kk < BASEQC_BASES; ++kk) cap_b[kk] += k == kk ? 1u : 0u;
+                    } else atomicAdd(&g_base[(e * BASEQC_CYCLES + bin) * BASEQC_BASES + k], 1ull);
+                    if (hq) {
+                        bqc_count(s_qs, v.blk + BQ_W_QUAL_SUM, e, bin, qv, cap_qs);
+                        bqc_count(s_qn, v.blk + BQ_W_QUAL_N, e, bin, 1u, cap_qn);
+                    }
+                };
+                const int32_t lead = (int32_t)((4 - ((uintptr_t)q & 3)) & 3), head = n < lead ? n : lead;
+                const int32_t nw = (n - head) >> 2, tail = n - head - 4 * nw;
+                if (sub < head) put(sub, q[sub]);
+                const uint32_t* w = (const uint32_t*)(q + head);
+                for (int32_t k = sub; k < nw; k += G) {
+                    const uint32_t x = w[k];
+                    const int64_t i0 = (int64_t)head + 4 * (int64_t)k;
+                    put(i0, x & 0xff); put(i0 + 1, x >> 8 & 0xff); put(i0 + 2, x >> 16 & 0xff); put(i0 + 3, x >> 24);
+                }
+                if (sub < tail) put((int64_t)head + 4 * (int64_t)nw + sub, q[head + 4 * nw + sub]);
+                // the capped last bin: once per record and lane
+                const int32_t last = e * BASEQC_CYCLES + BASEQC_CYCLES - 1;
+#pragma unroll
+                for (int kk = 0; kk < BASEQC_BASES; ++kk) if (cap_b[kk]) atomicAdd(&g_base[last * BASEQC_BASES + kk], (unsigned long long)cap_b[kk]);
+                if (cap_qs) atomicAdd(&v.blk[BQ_W_QUAL_SUM + last], cap_qs);
+                if (cap_qn) atomicAdd(&v.blk[BQ_W_QUAL_N + last], (unsigned long long)cap_qn);
+            }
+#pragma unroll
+            for (int m = G / 2; m > 0; m >>= 1) { gc += __shfl_xor(gc, m); acgt += __shfl_xor(acgt, m); }
+            if (have && sub == 0 && acgt) {
+                const int32_t b = r.e * BASEQC_GC_BINS + bqc_read_gc_bin(gc, acgt);
+                bqc_lds_add(&s_rgc[b], 1u, &v.blk[BQ_W_READ_GC + b]);
+            }
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < BASEQC_ENDS * BASEQC_LDS_CYCLES * BASEQC_BASES; j += BQC_THREADS)
+        if (s_base[j]) {
+            const int w = j / BASEQC_BASES;
+            atomicAdd(&g_base[((w / BASEQC_LDS_CYCLES) * BASEQC_CYCLES + w % BASEQC_LDS_CYCLES) * BASEQC_BASES + j % BASEQC_BASES], (unsigned long long)s_base[j]);
+        }
+    bqc_flush(s_qs, v.blk + BQ_W_QUAL_SUM, tid);
+    bqc_flush(s_qn, v.blk + BQ_W_QUAL_N, tid);
+    for (int j = tid; j < BASEQC_ENDS * BASEQC_GC_BINS; j += BQC_THREADS) if (s_rgc[j]) atomicAdd(&v.blk[BQ_W_READ_GC + j], (unsigned long long)s_rgc[j]);
+}
+
+// (c) the mapped primaries: aligned[], mism[], ins[], del_ev[], soft[] and the GC-bias window, by the same lane groups.  bqc_next has
+// passed bqc_mapped for the record before a reference byte is read: the whole span lies inside the contig, hence inside the packed
+// reference.  The lanes of a group share out the SEQ indices of every operation; the reference comes 16 bases per 32-bit load (a
+// one-word cache per lane, as PacCache); lanes 0..7 of the group take one word of the window each for the masked popcount.
+template <int G>
+__global__ void __launch_bounds__(BQC_THREADS) k_bqc_aligned(BqcView v)
+{
+    __shared__ uint32_t s_al[BASEQC_ENDS * BASEQC_LDS_CYCLES], s_mm[BASEQC_ENDS * BASEQC_LDS_CYCLES], s_in[BASEQC_ENDS * BASEQC_LDS_CYCLES],
+                        s_de[BASEQC_ENDS * BASEQC_LDS_CYCLES], s_so[BASEQC_ENDS * BASEQC_LDS_CYCLES];
+    __shared__ uint32_t s_gcb[3 * BASEQC_GC_BINS];                     // gcb_reads, gcb_qual_sum, gcb_qual_n: a few GC counts take nearly every record
+    const int tid = (int)threadIdx.x, sub = tid % G, per = BQC_THREADS / G;
+    for (int j = tid; j < BASEQC_ENDS * BASEQC_LDS_CYCLES; j += BQC_THREADS) { s_al[j] = 0; s_mm[j] = 0; s_in[j] = 0; s_de[j] = 0; s_so[j] = 0; }
+    for (int j = tid; j < 3 * BASEQC_GC_BINS; j += BQC_THREADS) s_gcb[j] = 0;
+    __syncthreads();
+    const uint32_t* const pacw = (const uint32_t*)v.pac;
+    unsigned long long skipped = 0;
+    for (int64_t first = (int64_t)blockIdx.x * per; first < v.n_items; first += (int64_t)gridDim.x * per) {
+        const int64_t i = first + tid / G;
+        int64_t o = 0, hi = 0;
+        if (i < v.n_items) { o = v.off[i]; hi = v.off[i + 1]; }
+        for (;;) {
+            BqcRec r = {};
+            const uint8_t* rec = nullptr;
+            const bool have = bqc_next(v, o, hi, true, rec, r);
+            if (!wave_any(have)) break;
+            // the window: its validity by every lane, its GC by the words
+            bool valid = false;
+            uint32_t g = 0;
+            int64_t ref0 = 0;
+            if (have) {
+                ref0 = v.ann_offset[r.refid];
+                const int64_t s = r.rev ? (int64_t)r.pos + r.span - BASEQC_WINDOW : (int64_t)r.pos;
+                valid = s >= 0 && s + BASEQC_WINDOW <= (int64_t)v.ann_len[r.refid] && bqc_window_clear(v.holes, v.n_holes, ref0 + s);
+                const int64_t a = ref0 + s, b = a + BASEQC_WINDOW, wd = (a >> 4) + sub;
+                if (valid && sub < 8 && wd * 16 < b) {
+                    const int64_t lo = a > wd * 16 ? a : wd * 16, up = b < wd * 16 + 16 ? b : wd * 16 + 16;
+                    g = (uint32_t)bqc_word_gc(*AS_GLOBAL(const uint32_t, pacw + wd), (int)(lo - wd * 16), (int)(up - wd * 16));
+                }
+            }
+            g += __shfl_xor(g, 4); g += __shfl_xor(g, 2); g += __shfl_xor(g, 1);       // lanes 0..7 of the group: all of the window's words
+            // the walk
+            unsigned long long qsum = 0;
+            if (have) {
+                const uint8_t* seq = rec + r.seq_off;
+                const uint8_t* q = rec + r.qual_off;
+                const int32_t e = r.e;
+                const bool wq = valid && r.l_seq > 0 && q[0] != 0xff;             // the window wants the sum of QUAL
+                uint32_t cap_al = 0, cap_mm = 0, cap_in = 0, cap_de = 0, cap_so = 0;
+                int64_t i0 = 0, p0 = ref0 + r.pos, cw = -1;
+                uint32_t cv = 0;
+                for (int32_t c = 0; c < r.n_cig; ++c) {
+                    const uint32_t x = bamsort_ld32(rec + r.cig_off + 4 * (int64_t)c), op = x & 0xf;
+                    const int64_t len = (int64_t)(x >> 4);
+                    if (op == 0 || op == 7 || op == 8) {
+                        // four consecutive bases per lane and step: their loads are issued together, then the counts
+                        for (int64_t j4 = 4 * (int64_t)sub; j4 < len; j4 += 4 * G) {
+                            const int nb = len - j4 < 4 ? (int)(len - j4) : 4;
+                            bool mm[4] = { false, false, false, false };
+#pragma unroll
+                            for (int u = 0; u < 4; ++u)
+                                if (u < nb) {
+                                    const int64_t p = p0 + j4 + u;
+                                    if (p >> 4 != cw) { cw = p >> 4; cv = *AS_GLOBAL(const uint32_t, pacw + cw); }
+                                    mm[u] = bqc_code(seq, i0 + j4 + u) != bqc_word_base(cv, (int)(p & 15));
+                                    if (wq) qsum += q[i0 + j4 + u];
+                                }
+#pragma unroll
+                            for (int u = 0; u < 4; ++u)
+                                if (u < nb) {
+                                    const int32_t bin = bqc_bin(r, i0 + j4 + u);
+                                    bqc_count(s_al, v.blk + BQ_W_ALIGNED, e, bin, 1u, cap_al);
+                                    if (mm[u]) bqc_count(s_mm, v.blk + BQ_W_MISM, e, bin, 1u, cap_mm);
+                                }
+                        }
+                        i0 += len; p0 += len;
+                    } else if (op == 1 || op == 4) {
+                        for (int64_t j = sub; j < len; j += G) {
+                            const int32_t bin = bqc_bin(r, i0 + j);
+                            if (op == 1) bqc_count(s_in, v.blk + BQ_W_INS, e, bin, 1u, cap_in);
+                            else bqc_count(s_so, v.blk + BQ_W_SOFT, e, bin, 1u, cap_so);
+                            if (wq) qsum += q[i0 + j];
+                        }
+                        i0 += len;
+                    } else if (op == 2) {
+                        if (sub == 0) bqc_count(s_de, v.blk + BQ_W_DEL, e, bqc_bin(r, i0 - 1), 1u, cap_de);
+                        p0 += len;
+                    } else if (op == 3) p0 += len;
+                }
+                const int32_t last = e * BASEQC_CYCLES + BASEQC_CYCLES - 1;       // the capped last bin: once per record and lane
+                if (cap_al) atomicAdd(&v.blk[BQ_W_ALIGNED + last], (unsigned long long)cap_al);
+                if (cap_mm) atomicAdd(&v.blk[BQ_W_MISM + last], (unsigned long long)cap_mm);
+                if (cap_in) atomicAdd(&v.blk[BQ_W_INS + last], (unsigned long long)cap_in);
+                if (cap_de) atomicAdd(&v.blk[BQ_W_DEL + last], (unsigned long long)cap_de);
+                if (cap_so) atomicAdd(&v.blk[BQ_W_SOFT + last], (unsigned long long)cap_so);
+            }
+#pragma unroll
+            for (int m = G / 2; m > 0; m >>= 1) qsum += __shfl_xor(qsum, m);
+            if (have && sub == 0) {
+                if (!valid) skipped += 1;
+                else {
+                    bqc_lds_add(&s_gcb[g], 1u, &v.blk[BQ_W_GCB_READS + g]);
+                    if (r.l_seq > 0 && rec[r.qual_off] != 0xff) {
+                        bqc_lds_add64(&s_gcb[BASEQC_GC_BINS + g], qsum, &v.blk[BQ_W_GCB_QUAL_SUM + g]);
+                        bqc_lds_add(&s_gcb[2 * BASEQC_GC_BINS + g], (uint32_t)r.l_seq, &v.blk[BQ_W_GCB_QUAL_N + g]);
+                    }
+                }
+            }
+        }
+    }
+    skipped = qc_wave_sum(skipped);
+    if ((tid & 63) == 0 && skipped) atomicAdd(&v.blk[BQ_W_GCB_SKIPPED], skipped);
+    __syncthreads();
+    bqc_flush(s_al, v.blk + BQ_W_ALIGNED, tid);
+    bqc_flush(s_mm, v.blk + BQ_W_MISM, tid);
+    bqc_flush(s_in, v.blk + BQ_W_INS, tid);
+    bqc_flush(s_de, v.blk + BQ_W_DEL, tid);
+    bqc_flush(s_so, v.blk + BQ_W_SOFT, tid);
+    for (int j = tid; j < 3 * BASEQC_GC_BINS; j += BQC_THREADS) if (s_gcb[j]) atomicAdd(&v.blk[BQ_W_GCB_READS + j], (unsigned long long)s_gcb[j]);      // (the three tables follow each other)
+}
+
+// windows[]: the valid window starts of the whole packed reference by GC count.  A workgroup stages a tile of GCW_TILE bases plus the
+// 25 bytes of the last start's window in LDS with coalesced 32-bit loads; a lane slides over GCW_RUN consecutive starts, adding the
+// base that enters and dropping the one that leaves.  The run's contig and its first hole come from one binary search each and are
+// walked from there.  (60 starts are 15 bytes: the lanes' bytes fall in different banks.)
+enum { GCW_THREADS = 256, GCW_RUN = 60, GCW_TILE = GCW_THREADS * GCW_RUN, GCW_BYTES = GCW_TILE / 4 + 28 };
+static_assert(GCW_RUN % 4 == 0 && GCW_BYTES % 4 == 0 && GCW_BYTES >= (GCW_TILE + BASEQC_WINDOW + 3) / 4, "a tile starts on a byte and holds the last window");
+__global__ void __launch_bounds__(GCW_THREADS) k_gc_windows(GcWinView v)
+{
+    __shared__ uint32_t s_pac[GCW_BYTES / 4];
+    __shared__ uint32_t s_h[BASEQC_GC_BINS];
+    const int tid = (int)threadIdx.x;
+    if (tid < BASEQC_GC_BINS) s_h[tid] = 0;
+    const uint8_t* const sb = (const uint8_t*)s_pac;
+    const int64_t n_tiles = (v.l_pac + GCW_TILE - 1) / GCW_TILE;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t t0 = tile * GCW_TILE, byte0 = t0 >> 2;
+        __syncthreads();                                                 // (the tile before is done with; s_h is zeroed)
+        for (int j = tid; j < GCW_BYTES / 4; j += GCW_THREADS)
+            s_pac[j] = byte0 + 4 * (int64_t)j < v.pac_bytes ? *AS_GLOBAL(const uint32_t, (const uint32_t*)(v.pac + byte0) + j) : 0u;
+        __syncthreads();
+        const int64_t g0 = t0 + (int64_t)tid * GCW_RUN, g1 = g0 + GCW_RUN < v.l_pac ? g0 + GCW_RUN : v.l_pac;
+        if (g0 >= g1) continue;
+        int32_t c = 0;
+        {   // the contig of g0: the last one that starts at or before it
+            int32_t lo = 0, hi = v.n_contigs - 1;
+            while (lo < hi) { const int32_t mid = lo + (hi - lo + 1) / 2; if (v.ann_offset[mid] <= g0) lo = mid; else hi = mid - 1; }
+            c = lo;
+        }
+        int64_t cend = v.ann_offset[c] + v.ann_len[c];
+        int32_t hk = bqc_first_hole(v.holes, v.n_holes, g0);
+        auto is_gc = [&](int64_t rel) { const uint32_t b = sb[rel >> 2] >> ((~rel & 3) << 1) & 3u; return (int32_t)((b ^ b >> 1) & 1u); };
+        int32_t gc = 0;
+        for (int j = 0; j < BASEQC_WINDOW; ++j) gc += is_gc(g0 - t0 + j);
+        for (int64_t g = g0; g < g1; ++g) {
+            while (g >= cend && c + 1 < v.n_contigs) { ++c; cend = v.ann_offset[c] + v.ann_len[c]; }
+            while (hk < v.n_holes && v.holes[hk].end <= g) ++hk;
+            if (g + BASEQC_WINDOW <= cend && (hk >= v.n_holes || v.holes[hk].off >= g + BASEQC_WINDOW)) bqc_lds_add(&s_h[gc], 1u, &v.out[gc]);
+            gc += is_gc(g - t0 + BASEQC_WINDOW) - is_gc(g - t0);
+        }
+    }
+    __syncthreads();
+    if (tid < BASEQC_GC_BINS && s_h[tid]) atomicAdd(&v.out[tid], (unsigned long long)s_h[tid]);
+}
+
 static int qc_grid(int64_t n_blocks, int n_cu, int per_cu)
 {
     const int64_t cap = (int64_t)(n_cu > 0 ? n_cu : 1) * per_cu;
@@ -1570,6 +1914,26 @@ void launch_qc_qual(hipStream_t st, const QcView& v, int max_len, int n_cu)
 {
     if (max_len > 1000) hipLaunchKernelGGL(k_qc_qual<64>, dim3(qc_grid(((int64_t)v.n_items + 3) / 4, n_cu, 16)), dim3(QC_THREADS), 0, st, v);      // long reads: a wavefront per read
     else hipLaunchKernelGGL(k_qc_qual<8>, dim3(qc_grid(((int64_t)v.n_items + 31) / 32, n_cu, 16)), dim3(QC_THREADS), 0, st, v);
+}
+// The grids of the base-level QC: k_bqc_bases keeps 22.2 KiB of LDS and k_bqc_aligned 16.2 KiB, so six and eight workgroups of four
+// waves fit a CU's 160 KiB beside each other with room to spare; the grid is that many per CU and strides over the rest.
+void launch_bqc_check(hipStream_t st, const BqcView& v, int n_cu)
+{
+    hipLaunchKernelGGL(k_bqc_check, dim3(qc_grid(((int64_t)v.n_items + BQC_THREADS - 1) / BQC_THREADS, n_cu, 8)), dim3(BQC_THREADS), 0, st, v);
+}
+void launch_bqc_bases(hipStream_t st, const BqcView& v, int max_len, int n_cu)
+{
+    if (max_len > 1000) hipLaunchKernelGGL(k_bqc_bases<64>, dim3(qc_grid(((int64_t)v.n_items + 3) / 4, n_cu, 6)), dim3(BQC_THREADS), 0, st, v);      // long reads: a wavefront per read
+    else hipLaunchKernelGGL(k_bqc_bases<8>, dim3(qc_grid(((int64_t)v.n_items + 31) / 32, n_cu, 6)), dim3(BQC_THREADS), 0, st, v);
+}
+void launch_bqc_aligned(hipStream_t st, const BqcView& v, int max_len, int n_cu)
+{
+    if (max_len > 1000) hipLaunchKernelGGL(k_bqc_aligned<64>, dim3(qc_grid(((int64_t)v.n_items + 3) / 4, n_cu, 8)), dim3(BQC_THREADS), 0, st, v);
+    else hipLaunchKernelGGL(k_bqc_aligned<8>, dim3(qc_grid(((int64_t)v.n_items + 31) / 32, n_cu, 8)), dim3(BQC_THREADS), 0, st, v);
+}
+void launch_gc_windows(hipStream_t st, const GcWinView& v, int n_cu)
+{
+    hipLaunchKernelGGL(k_gc_windows, dim3(qc_grid((v.l_pac + GCW_TILE - 1) / GCW_TILE, n_cu, 8)), dim3(GCW_THREADS), 0, st, v);
 }
 
 void launch_dup_entries(hipStream_t st, const DupView& v)

@@ -6,6 +6,7 @@
 #include "bam_sort.h"
 #include "bam_dup.h"
 #include "bam_qc.h"
+#include "bam_baseqc.h"
 #include "fastq_parse.h"
 #include "bgzf_inflate.h"
 
@@ -105,6 +106,13 @@ void launch_dup_flags(hipStream_t st, const DupView& v);
 // longest read).  Both run a fixed grid sized by the device's compute units.
 void launch_qc_records(hipStream_t st, const QcView& v, int n_cu);
 void launch_qc_qual(hipStream_t st, const QcView& v, int max_len, int n_cu);
+// Base-level QC (bam_baseqc.h): _check does every check and leaves the errors in word BQ_W_ERR of v.blk (zeroed by the caller),
+// records[], qcfail_skipped and the longest contributing read in BQ_W_MAX_LEN; when there is no error _bases and _aligned fill the
+// tables (max_len: that longest read).  _gc_windows: windows[] of the whole index into v.out (zeroed by the caller).
+void launch_bqc_check(hipStream_t st, const BqcView& v, int n_cu);
+void launch_bqc_bases(hipStream_t st, const BqcView& v, int max_len, int n_cu);
+void launch_bqc_aligned(hipStream_t st, const BqcView& v, int max_len, int n_cu);
+void launch_gc_windows(hipStream_t st, const GcWinView& v, int n_cu);
 
 // paired-end path (k_pe.hip)
 void launch_pestat_cand(hipStream_t st, const DevIndex& ix, const MemOpt& opt, const TileView& tv, int8_t* cand_dir, int64_t* cand_is);

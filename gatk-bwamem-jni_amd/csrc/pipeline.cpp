@@ -249,6 +249,8 @@ struct bwaidx_s {
     DevIndex d;
     DevBuf d_occ, d_sa_lo, d_sa_hi, d_pac, d_ann_off, d_ann_len, d_ann_alt, d_name_off, d_names, d_log, d_ptab;
     PairTab pair_tab;               // insert-size score terms of the running paired-end call (build_pair_tab)
+    DevBuf d_holes; int32_t n_holes = -1;      // the .amb holes as BqcHole, uploaded by the first base-level QC call of this replica (bam_baseqc.h)
+    std::vector<uint64_t> gc_windows;          // windows[] of bwamem_hip_index_gc_windows, once computed
     std::mutex mu;                  // one call at a time per index/device
     Workspace ws;
     std::vector<std::unique_ptr<Workspace>> extra_ws;   // further tiles in flight (one stream + host thread each)
@@ -376,6 +378,7 @@ struct bwamem_batch_s {
     SortBufs srt;
     DupBufs dup;                                     // bwamem_hip_batch_mark_duplicates
     DevBuf qc_blk;                                   // the block a QC add of this batch reduces into (bwamem_hip_qc_add_batch)
+    DevBuf baseqc_blk;                               // ... and a base-level QC add (bwamem_hip_baseqc_add_batch)
     DevBuf bai_win_base, bai_win, bai_winv, bai_cnt, bai_start, bai_cid, bai_chunks;   // the index (bwamem_hip_batch_index_bam)
     // what the records take from outside the response: base qualities laid out like d_raw (bwamem_hip_batch_set_qualities, or the
     // FASTQ text), names of the batch's own (bwamem_hip_batch_upload_fastq) and the read group (bwamem_hip_batch_set_read_group)
@@ -2628,27 +2631,35 @@ int bwamem_hip_qc_add_batch(bwamem_qc_t* q, bwamem_batch_t* b)
     });
 }
 
+// The places of the records of a host stream, and its end: the walk along block_size is the host's for such a stream, which carries
+// no other index of its records.  false with a message when the records do not chain to the end.
+static bool record_places(const char* what, const void* records, size_t nBytes, std::vector<int64_t>& off)
+{
+    off.clear();
+    const uint8_t* p = (const uint8_t*)records;
+    int64_t o = 0;
+    const int64_t hi = (int64_t)nBytes;
+    while (o < hi) {
+        int32_t bs = 0;
+        if (hi - o >= BAMSORT_MIN_REC) memcpy(&bs, p + o, 4);
+        const int64_t size = 4 + (int64_t)bs;
+        if (hi - o < BAMSORT_MIN_REC || size < BAMSORT_MIN_REC || size > hi - o) {
+            fprintf(stderr, "[bwamem_hip] %s: the records do not chain to the end of the stream (record %zu at byte %lld)\n", what, off.size(), (long long)o);
+            return false;
+        }
+        off.push_back(o); o += size;
+    }
+    off.push_back(o);
+    return true;
+}
+
 int bwamem_hip_qc_add_records_device(bwamem_qc_t* q, const void* records, size_t nBytes)
 {
     return guarded("bwamem_hip_qc_add_records_device", -1, [&]() -> int {
         if (!q || !q->idx || (nBytes && !records) || nBytes >= ((size_t)1 << 40)) return -1;
         if (nBytes == 0) return 0;
-        // the walk along block_size is the host's here: the stream carries no other index of its records
         std::vector<int64_t> off;
-        const uint8_t* p = (const uint8_t*)records;
-        int64_t o = 0;
-        const int64_t hi = (int64_t)nBytes;
-        while (o < hi) {
-            int32_t bs = 0;
-            if (hi - o >= BAMSORT_MIN_REC) memcpy(&bs, p + o, 4);
-            const int64_t size = 4 + (int64_t)bs;
-            if (hi - o < BAMSORT_MIN_REC || size < BAMSORT_MIN_REC || size > hi - o) {
-                fprintf(stderr, "[bwamem_hip] qc_add_records_device: the records do not chain to the end of the stream (record %zu at byte %lld)\n", off.size(), (long long)o);
-                return -1;
-            }
-            off.push_back(o); o += size;
-        }
-        off.push_back(o);
+        if (!record_places("qc_add_records_device", records, nBytes, off)) return -1;
         const size_t n_rec = off.size() - 1;
         bwaidx_s* ix = q->idx;
         std::lock_guard<std::mutex> lk(ix->mu);
@@ -2730,6 +2741,248 @@ int bwamem_hip_qc_add_serialized(bwamem_qc_t* q, const void* blob, size_t n)
         return 0;
     });
 }
+
+// ---- base-level QC (bam_baseqc.h; kernels next to k_qc_*).  Built like the QC above: the totals in host memory in the word layout of
+// the device's block, every add reduced into a zeroed block of its own on the batch's device and added only when its error word is
+// clear.  The reference, the contig table and the holes are those of the replica that holds the records.
+struct bwamem_baseqc_s {
+    bwaidx_s* idx = nullptr;
+    int32_t n_contigs = 0;
+    mutable std::mutex mu;
+    std::vector<uint64_t> w;        // BQ_WORDS
+};
+enum : uint64_t { BQ_BLOB_MAGIC = 0x0051424d454d4142ull /* "BAMEMBQ" */, BQ_BLOB_VERSION = 1 };
+enum { BQ_BLOB_HEAD = 4 };          // words before the block: magic, version, n_contigs, words of the block
+
+static void baseqc_add_words(bwamem_baseqc_s* q, const uint64_t* blk)
+{
+    std::lock_guard<std::mutex> lk(q->mu);
+    for (size_t i = BQ_W_RECORDS; i < (size_t)BQ_WORDS; ++i) q->w[i] += blk[i];      // (the error word and the device's longest read stay 0)
+}
+
+// the holes of ix on its device, once per replica.  The device of ix is current and its lock held.
+static bool baseqc_holes(bwaidx_s* ix)
+{
+    if (ix->n_holes >= 0) return true;
+    std::vector<BqcHole> hs;
+    for (const HoleInfo& h : ix->h.holes) if (h.len > 0) hs.push_back(BqcHole{ h.offset, h.offset + h.len });
+    std::sort(hs.begin(), hs.end(), [](const BqcHole& a, const BqcHole& b) { return a.off < b.off; });
+    if (hs.size() >= 0x7fffffffu || !ix->d_holes.ensure(hs.size() * sizeof(BqcHole) + 16)) return false;
+    if (!hs.empty()) HIP_OK(hipMemcpy(ix->d_holes.p, hs.data(), hs.size() * sizeof(BqcHole), hipMemcpyHostToDevice));
+    ix->n_holes = (int32_t)hs.size();
+    return true;
+}
+
+// The records at d_bam reduced into out (BQ_WORDS), as qc_reduce_device: the device of ix is current and its lock held.  Two host
+// waits: the errors with the longest read after the checks, and the block.
+static bool baseqc_reduce_device(bwaidx_s* ix, const uint8_t* d_bam, const int64_t* d_off, size_t n_items, bool grouped, DevBuf& blk, std::vector<uint64_t>& out)
+{
+    Workspace& ws = ix->ws;
+    if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+    if (n_items >= 0x7fffffffu) { fprintf(stderr, "[bwamem_hip] baseqc: too many records\n"); return false; }
+    if (!baseqc_holes(ix) || !blk.ensure((size_t)BQ_WORDS * 8)) return false;
+    HIP_OK(hipMemsetAsync(blk.p, 0, (size_t)BQ_WORDS * 8, ws.stream));
+    BqcView v; memset(&v, 0, sizeof v);
+    v.bam = d_bam; v.off = d_off; v.n_items = (int32_t)n_items; v.grouped = grouped ? 1 : 0; v.n_contigs = ix->d.n_seqs; v.n_holes = ix->n_holes;
+    v.pac = ix->d.pac; v.ann_offset = ix->d.ann_offset; v.ann_len = ix->d.ann_len; v.holes = ix->d_holes.as<BqcHole>(); v.blk = blk.as<unsigned long long>();
+    TIMED(ws, K_OTHER, launch_bqc_check(ws.stream, v, ix->d.n_cu));
+    HIP_OK(hipGetLastError());
+    uint64_t head[BQ_W_BASE];
+    HIP_OK(hipMemcpyAsync(head, blk.p, sizeof head, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 1: the errors and the longest read
+    const uint64_t e = head[BQ_W_ERR];
+    if (e) {
+        fprintf(stderr, "[bwamem_hip] baseqc: refused:%s%s%s%s\n", (e & BASEQC_ERR_WALK) ? " the records do not chain, or a record is shorter than its own fields;" : "",
+                (e & BASEQC_ERR_CONTIG) ? " a record names a contig the index does not have;" : "",
+                (e & BASEQC_ERR_CIGAR) ? " a mapped primary has no CIGAR, one that does not cover l_seq, or an H inside it;" : "",
+                (e & BASEQC_ERR_RANGE) ? " a mapped primary lies outside its contig;" : "");
+        return false;
+    }
+    const int max_len = (int)std::min<uint64_t>(head[BQ_W_MAX_LEN], 0x7fffffff);
+    TIMED(ws, K_OTHER, launch_bqc_bases(ws.stream, v, max_len, ix->d.n_cu));
+    TIMED(ws, K_OTHER, launch_bqc_aligned(ws.stream, v, max_len, ix->d.n_cu));
+    HIP_OK(hipGetLastError());
+    out.resize(BQ_WORDS);
+    HIP_OK(hipMemcpyAsync(out.data(), blk.p, (size_t)BQ_WORDS * 8, hipMemcpyDeviceToHost, ws.stream));
+    HIP_OK(hipStreamSynchronize(ws.stream));                           // wait 2: the block
+    return true;
+}
+
+// the block of a batch's records (empty: the batch has none); 0 = ok.  Takes the lock of the batch's replica.
+static int baseqc_batch_block(bwamem_baseqc_s* q, bwamem_batch_s* b, std::vector<uint64_t>& out)
+{
+    out.clear();
+    if (!q || !b || !b->idx) return -1;
+    if ((size_t)q->n_contigs != b->idx->h.contigs.size()) { fprintf(stderr, "[bwamem_hip] baseqc_add_batch: the batch's index has %zu contigs, the base-QC object %d\n", b->idx->h.contigs.size(), q->n_contigs); return -1; }
+    std::lock_guard<std::mutex> lk(b->idx->mu);
+    if (hipSetDevice(b->idx->device) != hipSuccess) return -1;
+    if (!b->bam_encoded) { fprintf(stderr, "[bwamem_hip] baseqc_add_batch: the batch holds no encoded records (bwamem_hip_batch_encode_bam)\n"); return -1; }
+    if (b->n_reads == 0 || b->bam_bytes == 0 || (b->bam_sorted && b->bam_n_rec == 0)) return 0;
+    const bool ok = b->bam_sorted ? baseqc_reduce_device(b->idx, b->bam.as<uint8_t>(), b->rec_dst.as<int64_t>(), b->bam_n_rec, false, b->baseqc_blk, out)
+                                  : baseqc_reduce_device(b->idx, b->bam.as<uint8_t>(), b->bam_off.as<int64_t>(), b->n_reads, true, b->baseqc_blk, out);
+    timed_collect(b->idx->ws);
+    if (!ok) out.clear();
+    return ok ? 0 : -1;
+}
+
+// (sam_writer.cpp) the two-step add of the one-call entry point, as bwamem_qc_batch_block / _commit
+int bwamem_baseqc_batch_block(bwamem_baseqc_t* q, bwamem_batch_t* b, uint64_t** blk)
+{
+    *blk = nullptr;
+    return guarded("bwamem_hip_fastq_to_bam_metrics", -1, [&]() -> int {
+        std::vector<uint64_t> out;
+        if (baseqc_batch_block(q, b, out) != 0) return -1;
+        if (out.empty()) return 0;
+        *blk = (uint64_t*)malloc(out.size() * 8);
+        if (!*blk) return -1;
+        memcpy(*blk, out.data(), out.size() * 8);
+        return 0;
+    });
+}
+void bwamem_baseqc_commit(bwamem_baseqc_t* q, const uint64_t* blk) { if (q && blk) baseqc_add_words(q, blk); }
+
+bwamem_baseqc_t* bwamem_hip_baseqc_create(bwaidx_t* idx)
+{
+    return guarded("bwamem_hip_baseqc_create", (bwamem_baseqc_t*)nullptr, [&]() -> bwamem_baseqc_t* {
+        if (!idx || idx->h.contigs.size() >= ((size_t)1 << 30)) return nullptr;
+        std::unique_ptr<bwamem_baseqc_s> q(new bwamem_baseqc_s());
+        q->idx = idx; q->n_contigs = (int32_t)idx->h.contigs.size();
+        q->w.assign(BQ_WORDS, 0);
+        return q.release();
+    });
+}
+void bwamem_hip_baseqc_free(bwamem_baseqc_t* q) { delete q; }
+
+int bwamem_hip_baseqc_add_batch(bwamem_baseqc_t* q, bwamem_batch_t* b)
+{
+    return guarded("bwamem_hip_baseqc_add_batch", -1, [&]() -> int {
+        std::vector<uint64_t> out;
+        if (baseqc_batch_block(q, b, out) != 0) return -1;
+        if (!out.empty()) baseqc_add_words(q, out.data());
+        return 0;
+    });
+}
+
+int bwamem_hip_baseqc_add_records_device(bwamem_baseqc_t* q, const void* records, size_t nBytes)
+{
+    return guarded("bwamem_hip_baseqc_add_records_device", -1, [&]() -> int {
+        if (!q || !q->idx || (nBytes && !records) || nBytes >= ((size_t)1 << 40)) return -1;
+        if (nBytes == 0) return 0;
+        std::vector<int64_t> off;
+        if (!record_places("baseqc_add_records_device", records, nBytes, off)) return -1;
+        const size_t n_rec = off.size() - 1;
+        bwaidx_s* ix = q->idx;
+        std::lock_guard<std::mutex> lk(ix->mu);
+        if (hipSetDevice(ix->device) != hipSuccess) return -1;
+        std::vector<uint64_t> out;
+        auto run = [&]() -> bool {
+            Workspace& ws = ix->ws;
+            if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+            DevBuf bam, d_off, blk;
+            if (!bam.ensure(nBytes + 8) || !d_off.ensure((n_rec + 1) * 8)) return false;
+            HIP_OK(hipMemcpyAsync(bam.p, records, nBytes, hipMemcpyHostToDevice, ws.stream));
+            HIP_OK(hipMemcpyAsync(d_off.p, off.data(), (n_rec + 1) * 8, hipMemcpyHostToDevice, ws.stream));
+            const bool ok = baseqc_reduce_device(ix, bam.as<uint8_t>(), d_off.as<int64_t>(), n_rec, false, blk, out);
+            HIP_OK(hipStreamSynchronize(ws.stream));
+            timed_collect(ws);
+            return ok;
+        };
+        if (!run()) return -1;
+        baseqc_add_words(q, out.data());
+        return 0;
+    });
+}
+
+int bwamem_hip_baseqc_counts(const bwamem_baseqc_t* q, bwamem_baseqc_counts_t* out)
+{
+    if (!q || !out) return -1;
+    std::lock_guard<std::mutex> lk(q->mu);
+    static_assert(sizeof(bwamem_baseqc_counts_t) == (BASEQC_ENDS + 2) * 8, "bwamem_baseqc_counts_t is the counter words in order");
+    memcpy(out, &q->w[BQ_W_RECORDS], sizeof *out);
+    return 0;
+}
+
+int64_t bwamem_hip_baseqc_array(const bwamem_baseqc_t* q, int which, uint64_t* dst, size_t cap)
+{
+    if (!q) return -1;
+    static const struct { size_t first, n; } tab[] = {
+        { BQ_W_BASE, (size_t)BQ_T * BASEQC_BASES }, { BQ_W_QUAL_SUM, BQ_T }, { BQ_W_QUAL_N, BQ_T }, { BQ_W_ALIGNED, BQ_T }, { BQ_W_MISM, BQ_T }, { BQ_W_INS, BQ_T },
+        { BQ_W_DEL, BQ_T }, { BQ_W_SOFT, BQ_T }, { BQ_W_READ_GC, BASEQC_ENDS * BASEQC_GC_BINS }, { BQ_W_GCB_READS, BASEQC_GC_BINS },
+        { BQ_W_GCB_QUAL_SUM, BASEQC_GC_BINS }, { BQ_W_GCB_QUAL_N, BASEQC_GC_BINS } };          // in the order of BWAMEM_HIP_BASEQC_*
+    static_assert(sizeof tab / sizeof tab[0] == BWAMEM_HIP_BASEQC_GCB_QUAL_N + 1, "one entry per array id");
+    if (which < 0 || which > BWAMEM_HIP_BASEQC_GCB_QUAL_N) return -1;
+    std::lock_guard<std::mutex> lk(q->mu);
+    if (dst) for (size_t i = 0; i < tab[which].n && i < cap; ++i) dst[i] = q->w[tab[which].first + i];
+    return (int64_t)tab[which].n;
+}
+
+void* bwamem_hip_baseqc_serialize(const bwamem_baseqc_t* q, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    if (!q) return nullptr;
+    std::lock_guard<std::mutex> lk(q->mu);
+    const size_t n = q->w.size();
+    uint64_t* p = (uint64_t*)malloc((BQ_BLOB_HEAD + n) * 8);
+    if (!p) return nullptr;
+    p[0] = BQ_BLOB_MAGIC; p[1] = BQ_BLOB_VERSION; p[2] = (uint64_t)q->n_contigs; p[3] = (uint64_t)n;
+    memcpy(p + BQ_BLOB_HEAD, q->w.data(), n * 8);
+    if (pBytes) *pBytes = (BQ_BLOB_HEAD + n) * 8;
+    return p;
+}
+
+int bwamem_hip_baseqc_add_serialized(bwamem_baseqc_t* q, const void* blob, size_t n)
+{
+    return guarded("bwamem_hip_baseqc_add_serialized", -1, [&]() -> int {
+        if (!q || !blob || n < BQ_BLOB_HEAD * 8) return -1;
+        uint64_t hd[BQ_BLOB_HEAD];
+        memcpy(hd, blob, sizeof hd);
+        if (hd[0] != BQ_BLOB_MAGIC || hd[1] != BQ_BLOB_VERSION) { fprintf(stderr, "[bwamem_hip] baseqc_add_serialized: not a base-QC blob of version %d\n", (int)BQ_BLOB_VERSION); return -1; }
+        if (hd[2] != (uint64_t)q->n_contigs || hd[3] != (uint64_t)q->w.size() || n != (BQ_BLOB_HEAD + q->w.size()) * 8) {
+            fprintf(stderr, "[bwamem_hip] baseqc_add_serialized: a blob of %llu contigs and %llu words in %zu bytes, this object has %d contigs and %zu words\n",
+                    (unsigned long long)hd[2], (unsigned long long)hd[3], n, q->n_contigs, q->w.size());
+            return -1;
+        }
+        std::vector<uint64_t> wds(q->w.size());
+        memcpy(wds.data(), (const uint8_t*)blob + BQ_BLOB_HEAD * 8, wds.size() * 8);
+        baseqc_add_words(q, wds.data());
+        return 0;
+    });
+}
+
+// windows[] of the index: computed on the handle's first replica the first time it is asked for, then kept
+int bwamem_hip_index_gc_windows(bwaidx_t* idx, uint64_t* out)
+{
+    return guarded("bwamem_hip_index_gc_windows", -1, [&]() -> int {
+        if (!idx || !out) return -1;
+        std::lock_guard<std::mutex> lk(idx->mu);
+        if (idx->gc_windows.empty()) {
+            if (hipSetDevice(idx->device) != hipSuccess) return -1;
+            auto run = [&]() -> bool {
+                Workspace& ws = idx->ws;
+                if (!ws.stream) HIP_OK(hipStreamCreate(&ws.stream));
+                DevBuf d_out;
+                if (!baseqc_holes(idx) || !d_out.ensure(BASEQC_GC_BINS * 8)) return false;
+                HIP_OK(hipMemsetAsync(d_out.p, 0, BASEQC_GC_BINS * 8, ws.stream));
+                GcWinView v; memset(&v, 0, sizeof v);
+                v.pac = idx->d.pac; v.l_pac = idx->d.l_pac; v.pac_bytes = ((idx->d.l_pac / 4 + 1) + 3) & ~(int64_t)3;      // (d_pac is longer than that)
+                v.ann_offset = idx->d.ann_offset; v.ann_len = idx->d.ann_len; v.n_contigs = idx->d.n_seqs; v.n_holes = idx->n_holes;
+                v.holes = idx->d_holes.as<BqcHole>(); v.out = d_out.as<unsigned long long>();
+                TIMED(ws, K_OTHER, launch_gc_windows(ws.stream, v, idx->d.n_cu));
+                HIP_OK(hipGetLastError());
+                std::vector<uint64_t> w(BASEQC_GC_BINS);
+                HIP_OK(hipMemcpyAsync(w.data(), d_out.p, BASEQC_GC_BINS * 8, hipMemcpyDeviceToHost, ws.stream));
+                HIP_OK(hipStreamSynchronize(ws.stream));
+                timed_collect(ws);
+                idx->gc_windows = std::move(w);
+                return true;
+            };
+            if (!run()) return -1;
+        }
+        memcpy(out, idx->gc_windows.data(), BASEQC_GC_BINS * 8);
+        return 0;
+    });
+}
+bwaidx_t* bwamem_baseqc_index(const bwamem_baseqc_t* q) { return q ? q->idx : nullptr; }      // (sam_writer.cpp: the GC report's windows[])
 
 static void bai_put(std::string& o, const void* p, size_t n) { o.append((const char*)p, n); }      // (the library is little-endian throughout)
 

@@ -38,6 +38,7 @@
 #include <vector>
 #include "bam_encode.h"
 #include "bam_qc.h"
+#include "bam_baseqc.h"
 #include "index_io.h"
 #include "../../include/bwamem_hip.h"
 
@@ -201,6 +202,10 @@ extern "C" {
 int bwamem_qc_batch_block(bwamem_qc_t* q, bwamem_batch_t* b, uint64_t** blk);
 void bwamem_qc_commit(bwamem_qc_t* q, const uint64_t* blk);
 const char* bwamem_qc_contig(const bwamem_qc_t* q, int i, int64_t* len);
+// the same two steps of the base-level QC accumulator, and its index
+int bwamem_baseqc_batch_block(bwamem_baseqc_t* q, bwamem_batch_t* b, uint64_t** blk);
+void bwamem_baseqc_commit(bwamem_baseqc_t* q, const uint64_t* blk);
+bwaidx_t* bwamem_baseqc_index(const bwamem_baseqc_t* q);
 }
 
 // A plain gzip stream (one or several concatenated members, as `gzip` writes them) inflated on the host through libz.so.1: such a
@@ -657,7 +662,8 @@ namespace {
 // totals, or null), sort if asked, compress, index if asked (fd_bai >= 0), write.  The header carries rg_line when there is one.
 // Everything is made before the first byte is written.
 int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* names, const int64_t* name_off, const char* rg_line, int mark_dup,
-                      bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, unsigned tags = 0, bwamem_qc_t* qc = nullptr)
+                      bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, unsigned tags = 0, bwamem_qc_t* qc = nullptr,
+                      bwamem_baseqc_t* bq = nullptr)
 {
     if (tags && bwamem_hip_batch_set_tags(b, tags) != 0) return -1;
     if (bwamem_hip_batch_encode_bam(b, paired, names, name_off) != 0) return -1;
@@ -665,6 +671,9 @@ int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* 
     uint64_t* qc_words_ = nullptr;                                      // the batch's QC block: reduced here, added when everything is written
     if (qc && bwamem_qc_batch_block(qc, b, &qc_words_) != 0) return -1;
     Freed qc_blk(qc_words_);
+    uint64_t* bq_words_ = nullptr;                                      // ... and its base-level QC block
+    if (bq && bwamem_baseqc_batch_block(bq, b, &bq_words_) != 0) return -1;
+    Freed bq_blk(bq_words_);
     if (sort && bwamem_hip_batch_sort_bam(b) != 0) return -1;
     size_t nh = 0, nzh = 0, nz = 0, nb = 0;
     Freed zh, z, bai;
@@ -688,6 +697,7 @@ int batch_to_bam_file(bwaidx_t* idx, bwamem_batch_t* b, int paired, const char* 
     if (z.p ? !write_all(fd, (const uint8_t*)z.p, nz) : !write_all(fd, BGZF_EOF, sizeof BGZF_EOF)) return -1;      // no record: the EOF block alone
     if (fd_bai >= 0 && !write_all(fd_bai, (const uint8_t*)bai.p, nb)) return -1;
     if (qc) bwamem_qc_commit(qc, (const uint64_t*)qc_blk.p);
+    if (bq) bwamem_baseqc_commit(bq, (const uint64_t*)bq_blk.p);
     return 0;
 }
 
@@ -717,7 +727,7 @@ int request_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, c
 
 int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const char* text1, size_t n1, const char* text2, size_t n2,
                       const char* rg_line, int mark_dup, bwamem_dup_counts_t* counts, int sort, int fd, int fd_bai, int write_header, bool gz = false, unsigned tags = 0,
-                      bwamem_qc_t* qc = nullptr)
+                      bwamem_qc_t* qc = nullptr, bwamem_baseqc_t* bq = nullptr)
 {
     try {
         if (!idx || !opt || fd < 0) return -1;
@@ -730,7 +740,7 @@ int fastq_to_bam_file(const char* what, bwaidx_t* idx, const mem_opt_t* opt, con
         if (!bo.b) return -1;
         if (rg_line && bwamem_hip_batch_set_read_group(bo.b, rg_line) != 0) return -1;
         if (bwamem_hip_batch_keep_offsets(bo.b, 1) != 0 || bwamem_hip_batch_align(idx, opt, pes, bo.b, 0) != 0) return -1;
-        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, mark_dup, counts, sort, fd, fd_bai, write_header, tags, qc);
+        return batch_to_bam_file(idx, bo.b, paired, nullptr, nullptr, rg_line, mark_dup, counts, sort, fd, fd_bai, write_header, tags, qc, bq);
     } catch (...) { return -1; }
 }
 
@@ -791,6 +801,13 @@ int bwamem_hip_fastq_to_bam(bwaidx_t* idx, const mem_opt_t* opt, const mem_pesta
 int bwamem_hip_fastq_to_bam_qc(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
                                const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts, bwamem_qc_t* qc)
 {
+    return bwamem_hip_fastq_to_bam_metrics(idx, opt, pes, in1, n1, in2, n2, o, fd, fd_bai, counts, qc, nullptr);
+}
+
+// ... and to a base-level QC accumulator (bam_baseqc.h) at the same point; either accumulator may be null
+int bwamem_hip_fastq_to_bam_metrics(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
+                                    const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts, bwamem_qc_t* qc, bwamem_baseqc_t* bq)
+{
     if (counts) memset(counts, 0, sizeof *counts);
     bwamem_bam_options_t v;
     memset(&v, 0, sizeof v);
@@ -803,7 +820,7 @@ int bwamem_hip_fastq_to_bam_qc(bwaidx_t* idx, const mem_opt_t* opt, const mem_pe
     const bool gz = is_gz(in1, n1);
     if (in2 && n2 && is_gz(in2, n2) != gz) { fprintf(stderr, "[bwamem_hip] fastq_to_bam: one input is compressed and the other is not\n"); return -1; }
     return fastq_to_bam_file("fastq_to_bam", idx, opt, pes, (const char*)in1, n1, (const char*)in2, n2, v.rg_line, v.mark_dup != 0, v.mark_dup ? counts : nullptr,
-                             v.sort != 0, fd, fd_bai, v.write_header, gz, v.tags, qc);
+                             v.sort != 0, fd, fd_bai, v.write_header, gz, v.tags, qc, bq);
 }
 
 // ---- the QC reports (bam_qc.h): plain text, '\n' line ends
@@ -883,6 +900,82 @@ char* bwamem_hip_qc_report(const bwamem_qc_t* q, int kind, size_t* pBytes)
                     snprintf(buf, sizeof buf, "%d\t%llu\t%llu\t%llu\n", v, (unsigned long long)h[0][v], (unsigned long long)h[1][v], (unsigned long long)h[2][v]);
                     o += buf;
                 }
+        } else return nullptr;
+        char* r = (char*)malloc(o.size() + 1);
+        if (!r) return nullptr;
+        memcpy(r, o.c_str(), o.size() + 1);
+        if (pBytes) *pBytes = o.size();
+        return r;
+    } catch (...) { return nullptr; }
+}
+
+// ---- the base-level QC reports (bam_baseqc.h): plain text, '\n' line ends.  Every double is a / b of two integers turned into
+// doubles at the end, printed with a fixed format; over an empty denominator it is 0.
+//   CYCLES   per end e with records: "# end <e> records <n>", the column names, and a row per cycle 0 .. the last one with a non-zero
+//            word in any table: cycle, bases (the sum of base[]), mean_quality (qual_sum / qual_n, %.4f), the fractions of A C G T N
+//            (%.6f), aligned, mismatch_rate (mism / aligned, %.6f), insertions, deletions, soft_clips
+//   GC       "# gcb_skipped <n>", the column names and 101 rows: gc, windows, reads, normalized_coverage ((reads[g] / sum reads) /
+//            (windows[g] / sum windows), computed as reads[g] * sum windows over sum reads * windows[g], %.6f), mean_base_quality
+//            (gcb_qual_sum / gcb_qual_n, %.4f); an empty line; "gc_percent<TAB>end0<TAB>end1<TAB>end2" and the 101 rows of read_gc
+char* bwamem_hip_baseqc_report(const bwamem_baseqc_t* q, int kind, size_t* pBytes)
+{
+    if (pBytes) *pBytes = 0;
+    try {
+        bwamem_baseqc_counts_t c;
+        if (!q || bwamem_hip_baseqc_counts(q, &c) != 0) return nullptr;
+        std::string o;
+        char buf[512];
+        auto array = [&](int which) { std::vector<uint64_t> a((size_t)std::max<int64_t>(bwamem_hip_baseqc_array(q, which, nullptr, 0), 0)); bwamem_hip_baseqc_array(q, which, a.data(), a.size()); return a; };
+        auto ratio = [](uint64_t a, uint64_t b) { return b ? (double)a / (double)b : 0.0; };
+        if (kind == BWAMEM_HIP_BASEQC_CYCLES) {
+            const std::vector<uint64_t> base = array(BWAMEM_HIP_BASEQC_BASE), qs = array(BWAMEM_HIP_BASEQC_QUAL_SUM), qn = array(BWAMEM_HIP_BASEQC_QUAL_N),
+                al = array(BWAMEM_HIP_BASEQC_ALIGNED), mm = array(BWAMEM_HIP_BASEQC_MISM), in = array(BWAMEM_HIP_BASEQC_INS), de = array(BWAMEM_HIP_BASEQC_DEL),
+                so = array(BWAMEM_HIP_BASEQC_SOFT);
+            for (int e = 0; e < BASEQC_ENDS; ++e) {
+                if (!c.records[e]) continue;
+                snprintf(buf, sizeof buf, "# end %d records %llu\n", e, (unsigned long long)c.records[e]);
+                o += buf;
+                o += "cycle\tbases\tmean_quality\tA\tC\tG\tT\tN\taligned\tmismatch_rate\tinsertions\tdeletions\tsoft_clips\n";
+                int last = -1;
+                for (int cy = 0; cy < BASEQC_CYCLES; ++cy) {
+                    const size_t w = (size_t)e * BASEQC_CYCLES + cy;
+                    uint64_t any = qs[w] | qn[w] | al[w] | mm[w] | in[w] | de[w] | so[w];
+                    for (int k = 0; k < BASEQC_BASES; ++k) any |= base[w * BASEQC_BASES + k];
+                    if (any) last = cy;
+                }
+                for (int cy = 0; cy <= last; ++cy) {
+                    const size_t w = (size_t)e * BASEQC_CYCLES + cy;
+                    uint64_t n = 0;
+                    for (int k = 0; k < BASEQC_BASES; ++k) n += base[w * BASEQC_BASES + k];
+                    snprintf(buf, sizeof buf, "%d\t%llu\t%.4f", cy, (unsigned long long)n, ratio(qs[w], qn[w]));
+                    o += buf;
+                    for (int k = 0; k < BASEQC_BASES; ++k) { snprintf(buf, sizeof buf, "\t%.6f", ratio(base[w * BASEQC_BASES + k], n)); o += buf; }
+                    snprintf(buf, sizeof buf, "\t%llu\t%.6f\t%llu\t%llu\t%llu\n", (unsigned long long)al[w], ratio(mm[w], al[w]), (unsigned long long)in[w],
+                             (unsigned long long)de[w], (unsigned long long)so[w]);
+                    o += buf;
+                }
+            }
+        } else if (kind == BWAMEM_HIP_BASEQC_GC) {
+            uint64_t win[BASEQC_GC_BINS];
+            if (bwamem_hip_index_gc_windows(bwamem_baseqc_index(q), win) != 0) return nullptr;
+            const std::vector<uint64_t> rd = array(BWAMEM_HIP_BASEQC_GCB_READS), gs = array(BWAMEM_HIP_BASEQC_GCB_QUAL_SUM), gn = array(BWAMEM_HIP_BASEQC_GCB_QUAL_N),
+                rg = array(BWAMEM_HIP_BASEQC_READ_GC);
+            uint64_t n_win = 0, n_rd = 0;
+            for (int g = 0; g < BASEQC_GC_BINS; ++g) { n_win += win[g]; n_rd += rd[g]; }
+            snprintf(buf, sizeof buf, "# gcb_skipped %llu\n", (unsigned long long)c.gcb_skipped);
+            o += buf;
+            o += "gc\twindows\treads\tnormalized_coverage\tmean_base_quality\n";
+            for (int g = 0; g < BASEQC_GC_BINS; ++g) {
+                const unsigned __int128 num = (unsigned __int128)rd[g] * n_win, den = (unsigned __int128)n_rd * win[g];
+                snprintf(buf, sizeof buf, "%d\t%llu\t%llu\t%.6f\t%.4f\n", g, (unsigned long long)win[g], (unsigned long long)rd[g], den ? (double)num / (double)den : 0.0,
+                         ratio(gs[g], gn[g]));
+                o += buf;
+            }
+            o += "\ngc_percent\tend0\tend1\tend2\n";
+            for (int g = 0; g < BASEQC_GC_BINS; ++g) {
+                snprintf(buf, sizeof buf, "%d\t%llu\t%llu\t%llu\n", g, (unsigned long long)rg[g], (unsigned long long)rg[BASEQC_GC_BINS + g], (unsigned long long)rg[2 * BASEQC_GC_BINS + g]);
+                o += buf;
+            }
         } else return nullptr;
         char* r = (char*)malloc(o.size() + 1);
         if (!r) return nullptr;

@@ -102,7 +102,8 @@ def align_shard(dll, idx, opts, reads, rank, world, paired=False, pes=None, dist
 def gather_qc(dist, qc, dst=0):
     """Whole-sample QC over the ranks (csrc/bam_qc.h): every rank's accumulator (a bwamem.BwaMemQc) is serialized and gathered, and
     rank `dst` adds the others' to its own -- the counters are sums, so nothing else is exchanged.  Returns qc on rank dst, None
-    elsewhere.  Every rank's index has the same contigs, so the blobs are of one size."""
+    elsewhere.  Every rank's index has the same contigs, so the blobs are of one size.  A bwamem.BwaMemBaseQc (csrc/bam_baseqc.h) has
+    the same serialize() / add() and is carried unchanged."""
     import torch
     dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
     mine = torch.frombuffer(bytearray(qc.serialize()), dtype=torch.uint8).to(dev)

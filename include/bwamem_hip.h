@@ -349,6 +349,51 @@ char*  bwamem_hip_qc_report(const bwamem_qc_t* q, int kind, size_t* pBytes);    
 int    bwamem_hip_fastq_to_bam_qc(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
                                   const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts, bwamem_qc_t* qc);
 
+/* Base-level QC on the device (csrc/bam_baseqc.h; additive like the QC above, and apart from it: bwamem_qc_t, its blob and its reports
+ * are what they were).  Quality, base composition, mismatches, insertions, deletions and soft clips per sequencing cycle and end, the
+ * reads' GC histograms, and GC bias over 100-base reference windows: what Picard MeanQualityByCycle, BaseDistributionByCycle and
+ * CollectGcBiasMetrics and the mismatch / indel / GC sections of `samtools stats` report, as a reduction over the records of a batch in
+ * HBM against the resident packed reference (no MD parsing, no FASTA).  The rule is at the top of csrc/bam_baseqc.h; parity with the
+ * output of those tools is not checked anywhere.  A bwamem_baseqc_t adds up calls, replicas and serialized accumulators like a
+ * bwamem_qc_t; a call that fails leaves it exactly as it was.
+ *   _baseqc_create     an empty accumulator for idx, which must outlive it.
+ *   _baseqc_add_batch  after _encode_bam; before or after _mark_duplicates and _sort_bam, with the same result.  Non-zero with a
+ *                      message without encoded records, for a batch of an index with another contig count, or when a record is refused
+ *                      (it does not parse; a mapped primary's CIGAR does not cover l_seq or has an inner H; it lies outside its
+ *                      contig).  0 and nothing added for a batch without records.
+ *   _baseqc_add_records_device   tooling: host bytes, any stream of BAM records, uploaded and reduced by the same kernels.
+ *   _baseqc_counts     the counters; _baseqc_array: one table (BWAMEM_HIP_BASEQC_*) into dst[0, cap), returns its length (dst may be
+ *                      NULL), -1 for an unknown table.  A table [e][c] has 3 x 1024 words, end e (0 unpaired or neither, 1 first, 2
+ *                      second) times cycle c, flattened in that order; _BASE is [e][c][k], k = A C G T N; _READ_GC is [e][101]; the
+ *                      _GCB_* have 101 words, one per GC count of the window.
+ *   _baseqc_serialize  as _qc_serialize (another magic); _baseqc_add_serialized refuses another version, n_contigs or size and then
+ *                      changes nothing.  windows[] is a property of the index and not part of the blob.
+ *   _baseqc_report     plain text as _qc_report.  _CYCLES: per end with records a header and one row per cycle up to the last non-zero
+ *                      one; _GC: per GC count the windows, the reads, the normalized coverage and the mean base quality, then the
+ *                      reads' GC histograms.  The formats are in csrc/sam_writer.cpp.
+ *   bwamem_hip_index_gc_windows   windows[g]: the number of 100-base windows of the index, over all contigs, that touch no .amb hole and
+ *                      hold g C/G bases (the denominator of GC bias); computed on the device once per handle.
+ *   bwamem_hip_fastq_to_bam_metrics   bwamem_hip_fastq_to_bam_qc with the batch also added to bq, at the same point and only if the whole
+ *                      call returns 0.  Either accumulator may be NULL. */
+typedef struct bwamem_baseqc_s bwamem_baseqc_t;
+typedef struct { uint64_t records[3], qcfail_skipped, gcb_skipped; } bwamem_baseqc_counts_t;
+enum { BWAMEM_HIP_BASEQC_BASE = 0, BWAMEM_HIP_BASEQC_QUAL_SUM, BWAMEM_HIP_BASEQC_QUAL_N, BWAMEM_HIP_BASEQC_ALIGNED, BWAMEM_HIP_BASEQC_MISM, BWAMEM_HIP_BASEQC_INS,
+       BWAMEM_HIP_BASEQC_DEL, BWAMEM_HIP_BASEQC_SOFT, BWAMEM_HIP_BASEQC_READ_GC, BWAMEM_HIP_BASEQC_GCB_READS, BWAMEM_HIP_BASEQC_GCB_QUAL_SUM,
+       BWAMEM_HIP_BASEQC_GCB_QUAL_N };
+enum { BWAMEM_HIP_BASEQC_CYCLES = 0, BWAMEM_HIP_BASEQC_GC };
+bwamem_baseqc_t* bwamem_hip_baseqc_create(bwaidx_t* idx);
+void   bwamem_hip_baseqc_free(bwamem_baseqc_t* q);
+int    bwamem_hip_baseqc_add_batch(bwamem_baseqc_t* q, bwamem_batch_t* b);
+int    bwamem_hip_baseqc_add_records_device(bwamem_baseqc_t* q, const void* records, size_t nBytes);
+int    bwamem_hip_baseqc_counts(const bwamem_baseqc_t* q, bwamem_baseqc_counts_t* out);
+int64_t bwamem_hip_baseqc_array(const bwamem_baseqc_t* q, int which, uint64_t* dst, size_t cap);
+void*  bwamem_hip_baseqc_serialize(const bwamem_baseqc_t* q, size_t* pBytes);              /* jnibwa_free */
+int    bwamem_hip_baseqc_add_serialized(bwamem_baseqc_t* q, const void* blob, size_t n);
+char*  bwamem_hip_baseqc_report(const bwamem_baseqc_t* q, int kind, size_t* pBytes);       /* jnibwa_free */
+int    bwamem_hip_index_gc_windows(bwaidx_t* idx, uint64_t out[101]);
+int    bwamem_hip_fastq_to_bam_metrics(bwaidx_t* idx, const mem_opt_t* opt, const mem_pestat_t* pes, const void* in1, size_t n1, const void* in2, size_t n2,
+                                       const bwamem_bam_options_t* o, int fd, int fd_bai, bwamem_dup_counts_t* counts, bwamem_qc_t* qc, bwamem_baseqc_t* bq);
+
 typedef struct {
     /* algorithmic counters */
     uint64_t n_reads, n_ext, n_lf, n_sa, n_dp_cells;
